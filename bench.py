@@ -10,6 +10,20 @@ loss, backward, gradient all-reduce over RCCL, gradient clipping and AdamW.  Inp
 in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
 value    = image pairs processed by all ranks / wall time (max over ranks) of K steps
+ms_per_step = milliseconds of one timed step (wall time of the K steps / K)
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything below -- the per-kernel timing pass,
+the short runs in other arithmetic / encoder configurations, the loss check against the reference fixture and the CPU
+baseline -- runs with --full only (the --no-* switches still turn single parts of it off).
+--dump-outputs DIR writes what one step of the timed path computes from the seeded inputs (rank 0): loss.npy and
+gradients.npy (every parameter's gradient, flattened in named_parameters() order), float32; a fixed, seeded sample of
+the gradients when they would exceed the size budget.  The timed steps train: the fp32 atomics of the backward pass sum
+in no fixed order, and the training steps amplify that rounding noise (two runs of the 30 steps of the default line end
+with losses 5e-3 apart).  So after the timed steps the initial weights and a fresh optimizer state are restored and the
+same step (the same captured graph) runs once more; its loss and gradients are what is written (two runs: 3e-7 and 7e-6
+apart).  The updated weights are not: AdamW's first step moves each one by ~lr * sign(gradient), so every gradient whose
+sign rounding decides moves its weight by up to 2 lr between two runs.
+
 roofline = the dominant hand-written kernel family of the step, timed per launch with events on
            the launching stream inside the timed region (achieved = algorithmic FLOPs or bytes of
            all its launches / their summed duration); `kernels` lists the other families the same
@@ -63,7 +77,48 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the exact-fp32 / north_star-encoder short runs and the loss check")
     ap.add_argument("--graph", type=int, default=-1,
                     help="1: capture the whole train step in a hipGraph and time replays; 0: eager; -1: auto")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the per-kernel timing pass, the "
+                    "exact-fp32 / north_star-encoder short runs, the loss check and the CPU baseline (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the step once more from the initial weights and write its loss "
+                         "and gradients as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_cpu_baseline = a.no_kernel_timing = a.no_extra = True
+    return a
+
+
+DUMP_MAX_ELEMS = 14 * 2 ** 20       # gradients: under 64 MB of float32
+
+
+def restore_initial_state(model, opt, initial):
+    """Parameters and buffers back to `initial` (their values before the first step) and the optimizer state to a fresh
+    one (moments and step count zero), in place: a captured graph keeps reading the same buffers."""
+    with torch.no_grad():
+        for t, v in zip(list(model.parameters()) + list(model.buffers()), initial):
+            t.copy_(v)
+        if hasattr(opt, "exp_avg"):                   # FlatAdamW
+            state = [opt.exp_avg, opt.exp_avg_sq, opt.step_count]
+        else:                                         # torch.optim.AdamW (created lazily, zero at the start)
+            state = [v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+        for t in state:
+            t.zero_()
+
+
+def dump_outputs(path, loss, model, grads):
+    """What the step computes: its loss and the parameters' gradients (grads: the step's FlatGradients), flattened.  More
+    than DUMP_MAX_ELEMS gradients are sampled at fixed, seeded positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    with torch.no_grad():
+        views = grads.views if grads is not None else {}
+        gr = torch.cat([(views[p] if p in views else (p.grad if p.grad is not None else torch.zeros_like(p))).reshape(-1)
+                        for _, p in named]).float().cpu().numpy()
+    if gr.size > DUMP_MAX_ELEMS:
+        gr = gr[np.sort(np.random.default_rng(0).choice(gr.size, DUMP_MAX_ELEMS, replace=False))]
+    np.save(os.path.join(path, "loss.npy"), np.asarray([float(loss)], dtype=np.float32))
+    np.save(os.path.join(path, "gradients.npy"), gr.astype(np.float32))
 
 
 def cpu_baseline(height, width, iters, batch):
@@ -399,6 +454,9 @@ def main():
         step = TrainStep(model, lr=1.6e-5, iters=a.iters, capturable=use_graph)
 
     eager_step = step
+    owner = sstep if semi else step                   # the TrainStep: optimizer and flat gradients
+    initial = ([t.detach().clone() for t in list(model.parameters()) + list(model.buffers())]
+               if a.dump_outputs else None)
     if split_graph:
         # At N > 1 every step of this run -- warm-up, the captured one, the eager kernel-timing pass -- exchanges gradients the
         # same way: ONE blocking all-reduce of the flat buffer between backward and the update, so the run issues a single
@@ -516,6 +574,14 @@ def main():
             rccl["per_rank_graph_fb_ms"] = [round(r[1], 3) for r in rows]
             rccl["per_rank_exchange_ms"] = [round(r[2], 3) for r in rows]
             rccl["per_rank_graph_up_ms"] = [round(r[3], 3) for r in rows]
+    loss_timed = float(loss) if loss is not None else None
+    if a.dump_outputs:
+        # (every rank: the step's exchange is a collective)
+        restore_initial_state(model, owner.opt, initial)
+        run()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, loss, model, owner.grads)
 
     # Per-launch kernel timing with events on the launching stream.  Eager steps are timed directly
     # inside the region above when --graph 0; with the hipGraph the same step is re-run eagerly right
@@ -538,10 +604,10 @@ def main():
         streams.OVERLAP = was_overlap
         ops.TIMER = None
         timer.steps = tsteps
-    if graph is not None:
-        run()
-        torch.cuda.synchronize()
-    loss_v = float(loss if loss is not None else loss_e)
+        if graph is not None:
+            run()
+            torch.cuda.synchronize()
+    loss_v = float(loss if loss is not None else loss_e) if timer is not None else loss_timed
 
     split_mode = os.environ.get("FSRAFT_CONV_SPLIT", "1") != "0"
     extra = {}
@@ -614,7 +680,7 @@ def main():
                                 f"all-reduce, clip, one AdamW step"),
                    "global_batch": B * world, "parallelism": f"dp{world}", "loss": loss_v,
                    "launch": (graph_note + " (the short runs behind value_exact_f32 / value_north_star_encoders and the "
-                              "per-kernel timing are eager)") if graph is not None else graph_note,
+                              "per-kernel timing are eager)") if graph is not None and a.full else graph_note,
                    "streams": ("one stream (--one-stream)" if not streams.OVERLAP else
                                "independent branches of the forward pass (context encoder | feature encoder + volume; the motion encoder's "
                                "flow | correlation branch; the flow-supervisor forward's uncropped-frame encodings | student iterations) on "

@@ -2373,6 +2373,46 @@ def test_bench_starts_its_own_ranks(tmp_path):
     assert all(p <= 1.15 * max(out["rccl"]["per_rank_ms_per_step"]) for p in parts), (parts, out["rccl"])
 
 
+def test_bench_plain_run_dumps_a_reproducible_step_and_full_run_adds_the_extras(tmp_path):
+    """A plain bench line carries the headline fields and no extras.  --dump-outputs writes the loss and gradients of one
+    step run from the seeded initial weights after the timed steps, as float32: two runs with different step counts
+    (different training trajectories) must write the same step up to summation-order rounding.  --full adds the
+    per-kernel timing pass to the same line."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--gpus", "1", "--height", "128", "--width", "192", "--iters", "3", "--batch-per-gpu", "1"]
+
+    def line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *small, *extra], cwd=str(tmp_path),
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    def dump(d):
+        return {n: np.load(tmp_path / d / f"{n}.npy") for n in ("loss", "gradients")}
+
+    out = line("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+    assert not {"kernels", "roofline", "cpu_baseline", "loss_check", "value_exact_f32"} & set(out)
+    a = dump("a")
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["gradients"].size > 1000 and np.abs(a["gradients"]).max() > 0
+    line("--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path / "b"))
+    b = dump("b")
+    assert abs(float(a["loss"][0]) - float(b["loss"][0])) <= 1e-5 * abs(float(b["loss"][0])), (a["loss"], b["loss"])
+    gd = np.linalg.norm(a["gradients"].astype(np.float64) - b["gradients"]) / np.linalg.norm(b["gradients"].astype(np.float64))
+    assert gd <= 1e-3, gd
+    full = line("--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra")
+    assert "kernels" in full and "roofline" in full and full["steps"] == 3
+
+
 def test_bench_rank_that_cannot_rendezvous_exits_with_a_message(tmp_path):
     """the first multi-GPU run must not hang.  A rank whose peers never arrive leaves the rendezvous after
     FSRAFT_DIST_TIMEOUT_S with exit code 3 and one line on stderr that names the rank and the rendezvous address."""

@@ -151,3 +151,75 @@ def test_flat_gradients_deferred_exchange():
     assert torch.equal(lin.weight.grad, torch.full((2, 3), 4.0)) and lin.weight.grad.data_ptr() == fg.views[lin.weight].data_ptr()
     fg.exchange_all()
     assert torch.equal(fg.views[lin.bias], torch.full((2,), 4.0))
+
+
+def test_bench_plain_run_is_lean_and_full_restores_the_extras(monkeypatch):
+    """A plain `bench.py` run does only what its headline needs: per-kernel timing, the short runs in other configurations,
+    the loss check and the CPU baseline run with --full only, where the --no-* switches still turn single parts off."""
+    import importlib
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_kernel_timing and a.no_extra and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out" and a.no_cpu_baseline
+    assert not a.no_kernel_timing and not a.no_extra
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: loss and gradients of the step as float32 .npy files, the gradients flattened in named_parameters()
+    order; past the size budget a fixed, seeded sample that is the same from run to run."""
+    import importlib
+    import os
+    import sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    from flow_supervisor_amd.parallel import FlatGradients
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(3, 2)
+    fg = FlatGradients(lin.parameters(), ["update.w", "update.b"])
+    fg.begin(exchange=False)
+    (lin(torch.arange(12.0).view(4, 3)) * torch.tensor([1.0, 2.0])).sum().backward()
+    fg.finish()
+    bench.dump_outputs(str(tmp_path / "a"), torch.tensor(1.5), lin, fg)
+    assert sorted(os.listdir(tmp_path / "a")) == ["gradients.npy", "loss.npy"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "gradients")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].tolist() == [1.5]
+    assert np.array_equal(got["gradients"], np.array([18, 22, 26, 36, 44, 52, 4, 8], dtype=np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 5)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor(1.5), lin, fg)
+    bench.dump_outputs(str(tmp_path / "c"), torch.tensor(1.5), lin, fg)
+    b, c = np.load(tmp_path / "b" / "gradients.npy"), np.load(tmp_path / "c" / "gradients.npy")
+    assert b.shape == (5,) and np.array_equal(b, c) and len(set(b.tolist())) == 5 and np.isin(b, got["gradients"]).all()
+
+
+def test_bench_restores_the_initial_state_in_place():
+    """--dump-outputs reruns the step from the initial weights and a fresh optimizer: parameters and buffers get their
+    saved values and the optimizer state its zeros, written into the same tensors (a captured graph reads those)."""
+    import importlib
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(3, 4), torch.nn.BatchNorm1d(4))
+    initial = [t.detach().clone() for t in list(m.parameters()) + list(m.buffers())]
+    opt = torch.optim.AdamW(m.parameters(), lr=1e-2)
+    for _ in range(3):
+        m(torch.randn(5, 3)).square().sum().backward()
+        opt.step()
+    held = [t.data_ptr() for t in list(m.parameters()) + list(m.buffers())]
+    state = [v for st in opt.state.values() for v in st.values() if torch.is_tensor(v)]
+    assert any(float(v.abs().sum()) > 0 for v in state)
+    bench.restore_initial_state(m, opt, initial)
+    now = list(m.parameters()) + list(m.buffers())
+    assert [t.data_ptr() for t in now] == held
+    assert all(torch.equal(t, v) for t, v in zip(now, initial))
+    assert all(float(v.abs().sum()) == 0 for v in state)

@@ -123,6 +123,7 @@ SIGNATURES = {
     "fsraft_corr_lookup_fwd_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
     "fsraft_set_norm_blocks": [c_int],
     "fsraft_get_tuning": [c_int],
+    "fsraft_conv_last_route": [c_int],
     "fsraft_space_to_depth2": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
     "fsraft_forward_interpolate": [c_void_p, c_void_p, c_int, c_int, _S],
     "fsraft_inorm_relu_cl_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _S],
@@ -158,6 +159,23 @@ SIGNATURES = {
                                 c_float, c_int, c_int, c_void_p, c_void_p, c_int, c_int, _S],
     "fsraft_corr_bwd_ktiles": [_PP, POINTER(c_int64), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p,
                                c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, _S],
+}
+
+# fsraft_conv_last_route codes (include/fsraft_tuning.h): which kernel the calling thread's last convolution ran.  The
+# arithmetic each one uses is the second field ("fp32" or "bf16x3").
+CONV_ROUTES = {
+    1: ("fwd.gemm32", "fp32"), 2: ("fwd.gemm64", "fp32"), 3: ("fwd.gemm64x128", "fp32"), 4: ("fwd.gemm128", "fp32"),
+    5: ("fwd.gemm64x64", "fp32"), 6: ("fwd.gemm64x64k16", "fp32"), 7: ("fwd.gemm64x128k16", "fp32"),
+    10: ("fwd.patch128x128", "bf16x3"), 11: ("fwd.patch256x128", "bf16x3"), 12: ("fwd.patch128x64", "bf16x3"),
+    13: ("fwd.patch256x64", "bf16x3"), 20: ("fwd.halo21", "bf16x3"), 21: ("fwd.halo22", "bf16x3"),
+    30: ("fwd.split64x256", "bf16x3"), 31: ("fwd.split256x64", "bf16x3"), 32: ("fwd.split256x128w16", "bf16x3"),
+    33: ("fwd.split128x128w8", "bf16x3"), 34: ("fwd.split64x128", "bf16x3"), 35: ("fwd.split128x128", "bf16x3"),
+}
+CONV_ROUTES.update({c + 100: (n + "+ksplit", a) for c, (n, a) in list(CONV_ROUTES.items()) if c >= 30})
+WGRAD_ROUTES = {
+    1: ("wgrad.exact32", "fp32"), 2: ("wgrad.exact64x64", "fp32"), 3: ("wgrad.exact128", "fp32"),
+    4: ("wgrad.split128", "bf16x3"), 5: ("wgrad.split128S", "bf16x3"), 6: ("wgrad.pack", "bf16x3"),
+    7: ("wgrad.patch", "bf16x3"), 8: ("wgrad.multi", "bf16x3"), 9: ("wgrad.multi_w8", "bf16x3"),
 }
 
 

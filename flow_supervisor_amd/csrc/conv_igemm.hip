@@ -1592,6 +1592,21 @@ using Cfg32 = GemmCfg<128, 32, 32, 4, 1, 2, 2>;
 using WCfg128 = GemmCfg<128, 128, 32, 2, 2, 0, 0>;
 using WCfg32 = GemmCfg<32, 128, 32, 1, 4, 0, 0>;
 
+// Route attestation (fsraft_conv_last_route, include/fsraft_tuning.h): every launch site records which kernel the calling
+// thread's last forward / data-gradient call (t_route[0]) and weight-gradient call (t_route[1]) ran.  Codes as in the header.
+thread_local int t_route[2] = {0, 0};
+template <class Cfg>
+constexpr int route_gemm() {
+  return std::is_same_v<Cfg, Cfg32> ? 1 : std::is_same_v<Cfg, Cfg64> ? 2 : std::is_same_v<Cfg, CfgM64> ? 3 :
+         std::is_same_v<Cfg, Cfg128> ? 4 : std::is_same_v<Cfg, Cfg6464> ? 5 : std::is_same_v<Cfg, Cfg6464K16> ? 6 :
+         std::is_same_v<Cfg, CfgM64K16> ? 7 : 0;
+}
+template <class Cfg>
+constexpr int route_split() {
+  return std::is_same_v<Cfg, SCfgN256> ? 30 : std::is_same_v<Cfg, SCfg256N64> ? 31 : std::is_same_v<Cfg, SCfg256W16> ? 32 :
+         std::is_same_v<Cfg, SCfg128W8> ? 33 : std::is_same_v<Cfg, SCfgM64> ? 34 : std::is_same_v<Cfg, SCfg128> ? 35 : 0;
+}
+
 // Fills the per-k-tile table of the buffer-addressed kernels; false when the shape does not fit its fields
 // (more than KTAB_MAX k-tiles, more than 15 taps, tap/channel offsets beyond 1 MiB, tensors of 2 GiB or more).
 bool build_ktab(const ConvArgs& a, ConvArgsT& t) {
@@ -1787,6 +1802,7 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
         p.ndst = 1; p.bias = nullptr; p.relu = 0; p.alpha = 1.0f;
         for (int i = 0; i < 3; ++i) p.rmask[i] = nullptr;
         dim3 g3(grid.x, grid.y, S);
+        t_route[0] = route_split<Cfg>() + 100;
         if (uni_tab) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 2>), g3, dim3(Cfg::NT), 0, s, t);
         else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 1>), g3, dim3(Cfg::NT), 0, s, t);
         int rc = fs_launch_status();
@@ -1802,6 +1818,7 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
   }
   if (buf && build_ktab_uniform(a, t)) {
     t.a.swz = swz;
+    t_route[0] = route_split<Cfg>();
     if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 2>), grid, dim3(Cfg::NT), 0, s, t);
     else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR, 2>), grid, dim3(Cfg::NT), 0, s, t);
     else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q, 2>), grid, dim3(Cfg::NT), 0, s, t);
@@ -1809,6 +1826,7 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
   }
   if (buf && build_ktab(a, t)) {
     t.a.swz = swz;
+    t_route[0] = route_split<Cfg>();
     if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 1>), grid, dim3(Cfg::NT), 0, s, t);
     else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR, 1>), grid, dim3(Cfg::NT), 0, s, t);
     else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q, 1>), grid, dim3(Cfg::NT), 0, s, t);
@@ -1817,6 +1835,7 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
   if constexpr (Cfg::NT != 256) {
     return -1;          // the wide configurations exist for the buffer-addressed paths only: caller falls back
   } else {
+  t_route[0] = route_split<Cfg>();
   if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN>), grid, dim3(256), 0, s, a);
   else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q>), grid, dim3(256), 0, s, a);
@@ -1831,10 +1850,12 @@ int launch_conv_split_plain(const ConvArgs& a, hipStream_t s) {
   dim3 grid(ceil_div(a.N, Cfg::BN), ceil_div(M, Cfg::BM));
   ConvArgsT t;
   if (build_ktab_uniform(a, t)) {
+    t_route[0] = route_split<Cfg>();
     hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 2>), grid, dim3(Cfg::NT), 0, s, t);
     return fs_launch_status();
   }
   if (build_ktab(a, t)) {
+    t_route[0] = route_split<Cfg>();
     hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 1>), grid, dim3(Cfg::NT), 0, s, t);
     return fs_launch_status();
   }
@@ -1845,6 +1866,7 @@ template <class Cfg>
 int launch_conv(const ConvArgs& a, int epi, hipStream_t s) {
   const int M = a.B * a.H * a.W;
   dim3 grid(ceil_div(a.N, Cfg::BN), ceil_div(M, Cfg::BM));
+  t_route[0] = route_gemm<Cfg>();
   if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_PLAIN>), grid, dim3(256), 0, s, a);
   else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_ZR>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_Q>), grid, dim3(256), 0, s, a);
@@ -1903,6 +1925,7 @@ extern "C" int fsraft_conv_forward(const fsraft_conv_desc* d, hipStream_t stream
   const bool want_stats = t_stat.sum != nullptr && d->epi == EPI_PLAIN && d->ndst == 1 && !d->relu && d->alpha == 1.0f && !d->dst_acc[0] &&
                           !d->rmask[0] && !d->bias && d->dst_n0[0] == 0 && d->N % 4 == 0;
   if (d->ws && (((uintptr_t)d->ws & 15) || d->ws_floats < 0)) return FS_ERR_ARG;
+  t_route[0] = 0;
   g_conv_ws = d->ws ? d->ws : t_reg_ws;                     // scratch of THIS call (thread_local: see the declaration)
   g_conv_ws_floats = d->ws ? d->ws_floats : t_reg_ws_floats;
   ConvArgs a{};
@@ -1955,6 +1978,7 @@ extern "C" int fsraft_conv_forward(const fsraft_conv_desc* d, hipStream_t stream
     // GEMM (96 -> 96 at 8x110x256: 249 vs 165 us; 128 -> 128 at 8x55x128: 93 vs 65 us), so only two-group layers come here.
     if (want_stats) { h.st_sum = t_stat.sum; h.st_sq = t_stat.sq; h.st_slots = t_stat.slots; halo_stats = true; }
     t_stat.done = halo_stats;
+    t_route[0] = d->N > 64 ? 21 : 20;
     return d->N > 64 ? launch_halo<2, 2>(h, stream) : launch_halo<2, 1>(h, stream);
   }
   if (d->N <= 32 && d->epi == EPI_PLAIN) return launch_conv<Cfg32>(a, d->epi, stream);
@@ -2033,6 +2057,10 @@ extern "C" int fsraft_conv_workspace(float* ws, int64_t floats) {
 
 // Reads back the arithmetic-mode switches (key 3: forward / data-gradient convolutions, key 4: weight gradients); the
 // host side uses it to skip packing the exact-fp32 weight matrices while the split-bf16 kernels are the ones that run.
+extern "C" int fsraft_conv_last_route(int which) {
+  return which == 0 || which == 1 ? t_route[which] : -1;
+}
+
 extern "C" int fsraft_get_tuning(int key) {
   if (key == 3) return g_conv_split;
   if (key == 4) return g_wgrad_split;
@@ -2094,6 +2122,7 @@ extern "C" int fsraft_conv_wgrad(const float* dy, int ldy, int Cout, const float
                                  const int* srcld, int nsrc, float* dwpk, float* dbias, int B, int H, int W, int KH,
                                  int KW, hipStream_t stream) {
   if (!dy || !src || !dwpk || nsrc < 1 || nsrc > 3 || ldy % 4 != 0) return FS_ERR_ARG;
+  t_route[1] = 0;
   WgradArgs a{};
   a.dy = dy; a.ldy = ldy; a.Cout = Cout;
   const bool small_m = Cout <= 32;
@@ -2141,6 +2170,7 @@ extern "C" int fsraft_conv_wgrad(const float* dy, int ldy, int Cout, const float
       a.xcd_xt = xt; a.xcd_yt = yt; a.xcd_groups = yt * (int)grid.z;
       grid = dim3((unsigned)(ceil_div(a.xcd_groups, 8) * 8 * xt), 1, 1);
     }
+    t_route[1] = 6;
     hipLaunchKernelGGL((conv_wgrad_pack_kernel<SWCfgPack>), grid, dim3(SWCfgPack::NT), 0, stream, a);
     return fs_launch_status();
   }
@@ -2158,17 +2188,20 @@ extern "C" int fsraft_conv_wgrad(const float* dy, int ldy, int Cout, const float
   a.dbias = dbias;
   const bool wbuf = g_wgrad_buf && chunk <= 32 * (WGRAD_MASK_WORDS - 2) && (int64_t)chunk * 4 * 2048 < 0x7fffffff;
   if (!small_m && !t64 && g_wgrad_split == 1) {
+    t_route[1] = 4;
     if (wbuf) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128, true>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128>), grid, dim3(256), 0, stream, a);
     return fs_launch_status();
   }
   if (!small_m && !t64 && g_wgrad_split == 2) {
+    t_route[1] = 5;
     if (wbuf) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S, true>), grid, dim3(256), 0, stream, a);
     else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S>), grid, dim3(256), 0, stream, a);
     return fs_launch_status();
   }
   // the exact-fp32 kernels do not fuse the bias gradient: separate column-sum pass
   if (dbias) { const int rc = fsraft_col_sum(dy, ldy, M, Cout, dbias, 1.0f, stream); if (rc) return rc; }
+  t_route[1] = small_m ? 1 : t64 ? 2 : 3;
   if (small_m) hipLaunchKernelGGL((conv_wgrad_kernel<WCfg32>), grid, dim3(256), 0, stream, a);
   else if (t64) hipLaunchKernelGGL((conv_wgrad_kernel<WCfg6464>), grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((conv_wgrad_kernel<WCfg128>), grid, dim3(256), 0, stream, a);
@@ -2183,6 +2216,7 @@ extern "C" int fsraft_conv_wgrad_multi(const float* const* dy, int nseg, int ldy
                                        const int* srcC, const int* srcld, int nsrc, float* dwpk, float* dbias, int B,
                                        int H, int W, int KH, int KW, hipStream_t stream) {
   if (!dy || !src || !dwpk || nseg < 1 || nsrc < 1 || nsrc > 3 || ldy % 4 != 0) return FS_ERR_ARG;
+  t_route[1] = 0;
   const int64_t M = (int64_t)B * H * W;
   const bool fast = g_wgrad_multi && nseg > 1 && Cout > 32 && g_wgrad_tile != 3 && g_wgrad_split == 2 && g_wgrad_buf;
   for (int base = 0; base < nseg; base += WGRAD_MAX_SEG) {
@@ -2242,6 +2276,7 @@ extern "C" int fsraft_conv_wgrad_multi(const float* const* dy, int nseg, int ldy
       m.a.xcd_xt = xt128; m.a.xcd_yt = ytiles; m.a.xcd_groups = ytiles * m.zs * n;
       grid = dim3((unsigned)(ceil_div(m.a.xcd_groups, 8) * 8 * xt128), 1, 1);
     }
+    t_route[1] = g_wgrad_w8 ? 9 : 8;
     if (g_wgrad_w8) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128W8, true, true>), grid, dim3(512), 0, stream, m);
     else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S, true, true>), grid, dim3(256), 0, stream, m);
     const int rc = fs_launch_status();

@@ -210,6 +210,7 @@ __global__ __launch_bounds__(PT_TH * 64) void conv_patch_kernel(const PatchArgs 
 
 template <int KH, int KW, int TH>
 int launch_conv_patch_t(const PatchArgs& p, int epi, dim3 grid, hipStream_t s) {
+  t_route[0] = (TH == 8 ? 11 : 10) + (KH == 3 && KW == 3 && p.a.N <= 64 ? 2 : 0);
   if constexpr (KH == 3 && KW == 3) {
     if (p.a.N <= 64) {                 // (plain epilogue only: checked by the caller)
       hipLaunchKernelGGL((conv_patch_kernel<EPI_PLAIN, 3, 3, TH, 64>), grid, dim3(TH * 64), 0, s, p);

@@ -291,6 +291,7 @@ int launch_wgrad_patch(WgradArgsM m, hipStream_t s) {
   // workgroup gets npair * nblk / 512 block-pairs (dealing whole ranges left the 3x3 256->192 and 1x5 384->256 layers with
   // 36-48 workgroups of 32 on some XCDs: two rounds).
   dim3 grid(8 * WP_SLOTS);
+  t_route[1] = 7;
   if (k33) hipLaunchKernelGGL((conv_wgrad_patch_kernel<3, 3>), grid, dim3(WP_NT), 0, s, p);
   else if (k15) hipLaunchKernelGGL((conv_wgrad_patch_kernel<1, 5>), grid, dim3(WP_NT), 0, s, p);
   else hipLaunchKernelGGL((conv_wgrad_patch_kernel<5, 1>), grid, dim3(WP_NT), 0, s, p);

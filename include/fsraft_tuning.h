@@ -28,6 +28,20 @@ extern "C" {
  * (-1 auto, 0 off, >= 2 forced). */
 int fsraft_set_tuning(int key, int value);
 int fsraft_get_tuning(int key);   /* keys 3 / 4 */
+/* Route attestation: the kernel the CALLING THREAD's last convolution ran (0 none / rejected call, -1 bad `which`).
+ * which 0, fsraft_conv_forward (forward and data-gradient calls):
+ *   exact-fp32 implicit GEMM tiles  1 Cfg32 (N <= 32, either mode), 2 Cfg64, 3 64x128, 4 128x128, 5 64x64 (key 0 = 3),
+ *                                   6 64x64 k16 (key 0 = 4), 7 64x128 k16 (key 0 = 5);
+ *   resident-patch kernel           10 128-pixel x 128-column tiles, 11 256 x 128, 12 128 x 64, 13 256 x 64 (conv_patch.inc);
+ *   conv3x3_halo_kernel             20 <2,1> (N <= 64), 21 <2,2>;
+ *   bf16x3 implicit GEMM tiles      30 64x256 (key 9 / key 3 = 5), 31 256x64, 32 256x128 sixteen waves, 33 128x128 eight
+ *                                   waves, 34 64x128, 35 128x128;
+ *   + 100: the same tile as split-K slices followed by conv_finish_kernel.
+ * which 1, fsraft_conv_wgrad / fsraft_conv_wgrad_multi (weight gradients):
+ *   1 exact 32x128 (Cout <= 32, either mode), 2 exact 64x64 (key 1 = 3), 3 exact 128x128, 4 bf16x3 128x128 (key 4 = 1),
+ *   5 bf16x3 128x128 single LDS image, 6 few-channel pack kernel, 7 resident-block kernel (wgrad_patch.inc), 8 multi-segment
+ *   launch, 9 multi-segment launch with eight-wave workgroups (key 15). */
+int fsraft_conv_last_route(int which);
 int fsraft_set_build_split(int on);   /* volume build: 1 bf16x3 (default), 0 exact fp32 MFMA */
 int fsraft_set_build_kernel(int which); /* record build: bits 8..15 start-up stagger of odd workgroups (x 64 x 127 cycles), bits 16..18 store policy (0 auto, 1 plain, 2 sc1, 3 nt) */
 /* cache policy of the tiled lookup's window loads: -1 auto (nt for volumes beyond the Infinity Cache; default), 0 plain, 2 nt,

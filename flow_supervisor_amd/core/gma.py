@@ -5,9 +5,13 @@
 ``GMAUpdateBlock`` (core/update.py) as v = to_v(motion), attn @ v, motion + gamma * out; the stand-alone
 ``Aggregate.forward`` here uses the same kernels for callers outside the update block.
 
-Single-head, content-only attention (the reference's default: train_gma.py:354, no --position_* flag) is the HIP
-path.  The optional relative-position terms (gma.py:6-31, 63-69) and multi-head maps are composed from torch
-tensor ops on the GPU around the same softmax; they are not part of the measured path.
+Single-head attention is the HIP path, for all three settings of the reference's flags (train_gma.py:350-354): content
+only (the default), --position_only and --position_and_content.  The relative-position terms (gma.py:6-31, 63-69) are h + w
+numbers per row of N = h * w logits: one small GEMM of the queries against the stacked slices of the two embedding tables
+gives them, and the softmax kernel adds them while the row is in LDS (`_AttentionFn` given the two tables, ops.softmax_rows_pos_), so no
+[N, N] positional tensor exists and the map can still leave as records.  Grids whose rows do not fit that kernel pair's LDS
+budget (ops.softmax_rows_pos_fits: 8 N + 4 (h + w) <= 65520 bytes, e.g. 55 x 128 fits, 64 x 128 does not), POS_HIP = False and
+multi-head maps are composed from torch tensor ops on the GPU (`Attention._forward_general`), dense and in fp32.
 """
 import torch
 from torch import nn
@@ -89,19 +93,46 @@ def is_records(t):
     return bool(getattr(t, "_fs_attn_records", False))
 
 
+# The relative-position terms on the HIP path (`_AttentionFn` with the two embedding tables, ops.softmax_rows_pos_).  False: the
+# torch-composed route of `Attention._forward_general`, which materialises the [B,1,N,N] positional scores and returns a dense map
+# -- the comparator of the tests and of scripts/gma_pos_attention_ab.py.
+POS_HIP = True
+
+
+def _pos_table_grad(dG, qk, B, N, D, R, scale):
+    """dT = scale * dG^T q over all B * N rows, [R, D]: the rows are cut into chunks of c (a divisor of N, <= 512), each chunk is
+    one batch entry of the exact NN GEMM on the transposed dG chunk, and the partial tables are added in chunk order (sum_n_): a
+    fixed summation order, no atomics, and B * N / c workgroup columns instead of one."""
+    c = max(d for d in range(1, min(N, 512) + 1) if N % d == 0)
+    nb = B * N // c
+    dGt = ops.transpose_batched(dG.view(nb, c, R))                       # [nb, R, c]
+    part = torch.empty(nb, R, D, device=dG.device, dtype=torch.float32)
+    ops.gemm_raw(dGt.data_ptr(), c, R * c, qk.data_ptr(), 2 * D, c * 2 * D, part.data_ptr(), D, R * D, nb, R, D, c, False, scale)
+    return ops.sum_n_(list(part.unbind(0)), torch.empty(R, D, device=dG.device, dtype=torch.float32))
+
+
 class _AttentionFn(torch.autograd.Function):
     """context [B,H,W,C] channels-last, to_qk weight [2D,C,1,1] -> softmax(scale q k^T) as [B,1,N,N] (records=True: as
-    records in that shape, see ATTN_RECORDS)."""
+    records in that shape, see ATTN_RECORDS).
+
+    With the RelPosEmb tables rel_h, rel_w ([2P-1, D] each) the logits are those of gma.py:62-69: T = the table rows an H x W
+    grid indexes (ops.rel_pos_table), G = scale q T^T [B,N,R], and the softmax kernel adds G[i, u-x+H-1] + G[i, (2H-1)+v-y+W-1]
+    to logit (i = (x,y), j = (u,v)) in LDS.  content=False (position_only): q k^T is neither computed nor allocated.  The caller
+    checks ops.softmax_rows_pos_fits(H, W)."""
 
     @staticmethod
-    def forward(ctx, x_cl, w, scale, records=False):
-        L.require_cuda_f32(x_cl, w)
+    def forward(ctx, x_cl, w, scale, records=False, rel_h=None, rel_w=None, content=True):
+        L.require_cuda_f32(x_cl, w, rel_h, rel_w)
         B, H, W, C = x_cl.shape
         D, N = w.shape[0] // 2, H * W
         w = w.detach().contiguous().float()
+        pos = rel_h is not None
+        content = bool(content) or not pos
         qk = _conv1x1(x_cl, w, C, 2 * D, B, H, W, 0)
         attn = torch.empty(B, 1, N, N, device=x_cl.device, dtype=torch.float32)
-        if ops.SPLIT_VOLUME_BWD and D % 32 == 0:          # record GEMM core: q and k are record slices of one [N][2D] tensor
+        if not content:
+            pass
+        elif ops.SPLIT_VOLUME_BWD and D % 32 == 0:          # record GEMM core: q and k are record slices of one [N][2D] tensor
             qkr = ops.to_records(qk.view(B, N, 2 * D))
             ops.gemm_rec_nt_raw(qkr.data_ptr(), 2 * D, N * 2 * D, qkr.data_ptr() + 4 * D, 2 * D, N * 2 * D, attn.data_ptr(), N, N * N,
                                 B, N, N, D, scale)
@@ -109,27 +140,42 @@ class _AttentionFn(torch.autograd.Function):
             ops.gemm_raw(qk.data_ptr(), 2 * D, N * 2 * D, qk.data_ptr() + 4 * D, 2 * D, N * 2 * D, attn.data_ptr(), N, N * N,
                          B, N, N, D, True, scale)
         records = bool(records) and _records_ok(D, N)
-        if records:
+        T = None
+        if pos:
+            T, R, sh, sw = ops.rel_pos_table(rel_h, rel_w, H, W)
+            ctx.rel_slices = (sh, sw)
+            G = torch.empty(B, N, R, device=x_cl.device, dtype=torch.float32)
+            ops.gemm_raw(qk.data_ptr(), 2 * D, N * 2 * D, T.data_ptr(), D, 0, G.data_ptr(), R, N * R, B, N, R, D, True, scale)
+            ops.softmax_rows_pos_(attn, G, H, W, content, records)
+        elif records:
             ops.softmax_rows_rec_(attn)
         else:
             ops.softmax_rows_(attn)
-        ctx.save_for_backward(x_cl, w, qk, attn)
-        ctx.scale, ctx.records = scale, records
+        ctx.save_for_backward(x_cl, w, qk, attn, T, rel_h, rel_w)
+        ctx.scale, ctx.records, ctx.content = scale, records, content
         return attn
 
     @staticmethod
     def backward(ctx, dA):
-        x_cl, w, qk, attn = ctx.saved_tensors
+        x_cl, w, qk, attn, T, rel_h, rel_w = ctx.saved_tensors
         B, H, W, C = x_cl.shape
         D, N, scale = w.shape[0] // 2, H * W, ctx.scale
         # (the gradient tensor is overwritten: _AttnFn.backward allocates it for us and says so; anything else is copied first)
         own = bool(getattr(dA, "_fs_owned", False)) and dA.is_contiguous()
         dA = dA if own else dA.contiguous().clone()
-        dS = ops.softmax_rows_bwd_rec_(attn, dA) if ctx.records else ops.softmax_rows_bwd_(attn, dA)
+        dG = None
+        if T is not None:
+            dG = torch.empty(B, N, T.shape[0], device=dA.device, dtype=torch.float32)
+            dS = ops.softmax_rows_pos_bwd_(attn, dA, dG, H, W, ctx.records)
+        else:
+            dS = ops.softmax_rows_bwd_rec_(attn, dA) if ctx.records else ops.softmax_rows_bwd_(attn, dA)
         del dA
         dqk = torch.empty_like(qk)
         # dq = scale dS k ; dk = scale dS^T q
-        if ops.SPLIT_VOLUME_BWD and D % 32 == 0:
+        if not ctx.content:                 # position_only: the logits do not depend on k, dq comes from dG alone
+            del dS
+            dqk[..., D:].zero_()
+        elif ops.SPLIT_VOLUME_BWD and D % 32 == 0:
             # record GEMM core: dS split to records once; dq = dS . (k^T)^T with k^T [D][N] (rows of records along j),
             # dk = dS^T . q with both operands read k-major (records along the output index)
             dSr = dS.view(B, N, N) if ctx.records else ops.to_records(dS.view(B, N, N))
@@ -141,23 +187,38 @@ class _AttentionFn(torch.autograd.Function):
                                 scale, ksplit=2)
             ops.gemm_rec_tn_raw(dSr.data_ptr(), Nr, N * Nr, qkr.data_ptr(), 2 * D, N * 2 * D, dqk.data_ptr() + 4 * D, 2 * D, N * 2 * D,
                                 B, N, D, N, scale, ksplit=2)
-            dw = _conv1x1_wgrad(dqk, x_cl, C, 2 * D, B, H, W) if ctx.needs_input_grad[1] else None
-            dx = _conv1x1(dqk, w, C, 2 * D, B, H, W, 1) if ctx.needs_input_grad[0] else None
-            return dx, dw, None, None
-        dSt = ops.transpose_batched(dS.view(B, N, N))        # tiled transpose: 4-6 TB/s, the strided copy reaches 1.5-2
-        if N % 4 == 0 and D % 4 == 0:      # k-major operands on the transposed-read split-bf16 GEMM
-            ops.gemm_tn_raw(dSt.data_ptr(), N, N * N, qk.data_ptr() + 4 * D, 2 * D, N * 2 * D, dqk.data_ptr(), 2 * D,
-                            N * 2 * D, B, N, D, N, scale)
-            ops.gemm_tn_raw(dS.data_ptr(), N, N * N, qk.data_ptr(), 2 * D, N * 2 * D, dqk.data_ptr() + 4 * D, 2 * D,
-                            N * 2 * D, B, N, D, N, scale)
+            del dSr
         else:
-            ops.gemm_raw(dS.data_ptr(), N, N * N, qk.data_ptr() + 4 * D, 2 * D, N * 2 * D, dqk.data_ptr(), 2 * D,
-                         N * 2 * D, B, N, D, N, False, scale)
-            ops.gemm_raw(dSt.data_ptr(), N, N * N, qk.data_ptr(), 2 * D, N * 2 * D, dqk.data_ptr() + 4 * D, 2 * D,
-                         N * 2 * D, B, N, D, N, False, scale)
+            dSt = ops.transpose_batched(dS.view(B, N, N))        # tiled transpose: 4-6 TB/s, the strided copy reaches 1.5-2
+            if N % 4 == 0 and D % 4 == 0:      # k-major operands on the transposed-read split-bf16 GEMM
+                ops.gemm_tn_raw(dSt.data_ptr(), N, N * N, qk.data_ptr() + 4 * D, 2 * D, N * 2 * D, dqk.data_ptr(), 2 * D,
+                                N * 2 * D, B, N, D, N, scale)
+                ops.gemm_tn_raw(dS.data_ptr(), N, N * N, qk.data_ptr(), 2 * D, N * 2 * D, dqk.data_ptr() + 4 * D, 2 * D,
+                                N * 2 * D, B, N, D, N, scale)
+            else:
+                ops.gemm_raw(dS.data_ptr(), N, N * N, qk.data_ptr() + 4 * D, 2 * D, N * 2 * D, dqk.data_ptr(), 2 * D,
+                             N * 2 * D, B, N, D, N, False, scale)
+                ops.gemm_raw(dSt.data_ptr(), N, N * N, qk.data_ptr(), 2 * D, N * 2 * D, dqk.data_ptr() + 4 * D, 2 * D,
+                             N * 2 * D, B, N, D, N, False, scale)
+            del dS, dSt
+        drh = drw = None
+        if dG is not None:
+            # dq (+)= scale dG T ; dT = scale dG^T q, its two row blocks added into the table slices the grid indexes
+            R = T.shape[0]
+            ops.gemm_raw(dG.data_ptr(), R, N * R, T.data_ptr(), D, 0, dqk.data_ptr(), 2 * D, N * 2 * D, B, N, D, R, False, scale,
+                         accumulate=ctx.content)
+            if ctx.needs_input_grad[4] or ctx.needs_input_grad[5]:
+                dT = _pos_table_grad(dG, qk, B, N, D, R, scale)
+                sh, sw = ctx.rel_slices
+                if ctx.needs_input_grad[4]:
+                    drh = torch.zeros_like(rel_h)
+                    drh[sh] = dT[:2 * H - 1]
+                if ctx.needs_input_grad[5]:
+                    drw = torch.zeros_like(rel_w)
+                    drw[sw] = dT[2 * H - 1:2 * H + 2 * W - 2]
         dw = _conv1x1_wgrad(dqk, x_cl, C, 2 * D, B, H, W) if ctx.needs_input_grad[1] else None
         dx = _conv1x1(dqk, w, C, 2 * D, B, H, W, 1) if ctx.needs_input_grad[0] else None
-        return dx, dw, None, None
+        return dx, dw, None, None, drh, drw, None
 
 
 class Attention(nn.Module):
@@ -175,20 +236,45 @@ class Attention(nn.Module):
     def _positional(self):
         return bool(getattr(self.args, "position_only", False) or getattr(self.args, "position_and_content", False))
 
+    def _pos_hip(self, H, W, C):
+        """True where the positional flags run on the kernels: one head, POS_HIP, channels in fours and a row that fits the
+        softmax pair's LDS budget.  A grid larger than max_pos_size has no embedding rows to index (the reference fails there
+        with an indexing error): ValueError, on either route."""
+        if self.heads != 1 or not self._positional():
+            return False
+        P = (self.pos_emb.rel_height.weight.shape[0] + 1) // 2
+        if H > P or W > P:
+            raise ValueError(f"relative-position attention on a {H} x {W} grid: max_pos_size is {P}")
+        return POS_HIP and C % 4 == 0 and ops.softmax_rows_pos_fits(H, W)
+
+    def _apply_pos(self, fmap_cl, records):
+        content = not getattr(self.args, "position_only", False)         # (position_only wins, as in gma.py:62-68)
+        return _AttentionFn.apply(fmap_cl, self.to_qk.weight, self.scale, records, self.pos_emb.rel_height.weight,
+                                  self.pos_emb.rel_width.weight, content)
+
     @L.on_tensor_device
     def forward(self, fmap):
         if self.heads == 1 and not self._positional() and fmap.shape[1] % 4 == 0:
             return self.forward_cl(to_channels_last(fmap.float()))
+        if self._pos_hip(fmap.shape[2], fmap.shape[3], fmap.shape[1]):
+            return self._apply_pos(to_channels_last(fmap.float()), False)
         return self._forward_general(fmap)
 
     @L.on_tensor_device
     def forward_cl(self, fmap_cl, records=False):
-        """Channels-last entry (content-only, single head): [B,H,W,dim] -> [B,1,N,N].  records=True (the update block's
-        forward_cl is the consumer): the map may come back as records in that shape (ATTN_RECORDS above; `is_records`)."""
+        """Channels-last entry (single head): [B,H,W,dim] -> [B,1,N,N].  records=True (the update block's forward_cl is the
+        consumer): the map may come back as records in that shape (ATTN_RECORDS above; `is_records`).  With a positional flag
+        the same holds where `_pos_hip` says so; elsewhere (rows over the LDS budget, POS_HIP off, several heads) the map is
+        the dense one of the torch-composed route."""
+        _, H, W, C = fmap_cl.shape
+        D = self.to_qk.weight.shape[0] // 2
+        if self._pos_hip(H, W, C):
+            if records and _records_ok(D, H * W):
+                return mark_records(self._apply_pos(fmap_cl, True))
+            return self._apply_pos(fmap_cl, False)
         if self.heads != 1 or self._positional():
             return self._forward_general(from_channels_last(fmap_cl))
-        _, H, W, _ = fmap_cl.shape
-        if records and _records_ok(self.to_qk.weight.shape[0] // 2, H * W):
+        if records and _records_ok(D, H * W):
             return mark_records(_AttentionFn.apply(fmap_cl, self.to_qk.weight, self.scale, True))
         return _AttentionFn.apply(fmap_cl, self.to_qk.weight, self.scale)
 

@@ -740,6 +740,59 @@ def softmax_rows_bwd_rec_(Ar, dA):
     return dA
 
 
+POS_LDS_LIMIT = 65536 - 16     # dynamic LDS of a launch without an opt-in, less the kernels' static reduction words
+
+
+def softmax_rows_pos_fits(h, w):
+    """The shapes fsraft_softmax_rows_pos AND its backward take: two rows of n = h * w floats plus h + w sums in LDS."""
+    return 8 * ((h * w + 3) & ~3) + 4 * (h + w) <= POS_LDS_LIMIT
+
+
+def rel_pos_table(rel_height_w, rel_width_w, h, w):
+    """The rows of the two RelPosEmb tables ([2P-1, D] each, gma.py:13-18) an h x w grid indexes, stacked: returns
+    (T [rows, D], rows, slice into rel_height.weight, slice into rel_width.weight).  T[:2h-1] = rel_height.weight[P-h : P+h-1]
+    (offsets u - x = -(h-1) .. h-1), T[2h-1 : 2h+2w-2] = rel_width.weight[P-w : P+w-1]; rows = 2h + 2w - 2 rounded up to a
+    multiple of 4 (16-byte rows of the score matrix and the vector path of fsraft_gemm_f32), the padding rows zero."""
+    P = (rel_height_w.shape[0] + 1) // 2
+    if h > P or w > P:
+        raise ValueError(f"relative-position attention on a {h} x {w} grid: max_pos_size is {P}")
+    sh, sw = slice(P - h, P + h - 1), slice(P - w, P + w - 1)
+    used = 2 * h + 2 * w - 2
+    rows = (used + 3) & ~3
+    T = torch.zeros(rows, rel_height_w.shape[1], device=rel_height_w.device, dtype=torch.float32)
+    T[:2 * h - 1] = rel_height_w.detach()[sh]
+    T[2 * h - 1:used] = rel_width_w.detach()[sw]
+    return T, rows, sh, sw
+
+
+def softmax_rows_pos_(S, G, h, w, content=True, records=False):
+    """In-place softmax over the last dimension of S [..., n, n] (n = h * w) with the relative-position logits of gma.py:6-31
+    added in LDS: row i = (x, y), column (u, v) gets G[i, u - x + h - 1] + G[i, (2h - 1) + v - y + w - 1], G [..., n, ldg] the
+    scores of the queries against rel_pos_table.  content=False: S is written without being read (position_only).
+    records=True: the result overwrites S as records (softmax_rows_rec_)."""
+    L.require_cuda_f32(S, G)
+    n, ldg = S.shape[-1], G.shape[-1]
+    rows = S.numel() // n
+    if not (S.is_contiguous() and G.is_contiguous()) or G.numel() != rows * ldg:
+        raise ValueError("softmax_rows_pos_: contiguous S [..., n, n] and G [..., n, ldg]")
+    L.check(_lib().fsraft_softmax_rows_pos(L.ptr(S), L.ptr(G), ldg, rows, n, h, w, int(bool(content)), int(bool(records)),
+                                           L.stream()), "softmax_rows_pos")
+    return S
+
+
+def softmax_rows_pos_bwd_(A, dA, dG, h, w, records=False):
+    """dA <- dS = A * (dA - sum(dA * A, -1)) in place (records=True: A holds records, dS is written as records) and
+    dG [..., n, ldg] <- the gradient of softmax_rows_pos_'s G, every column written.  Returns dA."""
+    L.require_cuda_f32(A, dA, dG)
+    n, ldg = A.shape[-1], dG.shape[-1]
+    rows = A.numel() // n
+    if not (A.is_contiguous() and dA.is_contiguous() and dG.is_contiguous()) or dA.numel() != A.numel() or dG.numel() != rows * ldg:
+        raise ValueError("softmax_rows_pos_bwd_: contiguous A, dA [..., n, n] and dG [..., n, ldg]")
+    L.check(_lib().fsraft_softmax_rows_pos_bwd(L.ptr(A), L.ptr(dA), L.ptr(dG), ldg, rows, n, h, w, int(bool(records)), L.stream()),
+            "softmax_rows_pos_bwd")
+    return dA
+
+
 def gma_mix_fwd(x, y, gamma, dst):
     """dst = x + gamma * y over V channel slices (gma.py:113); gamma: 1-element device tensor."""
     M = x.t.numel() // x.ld

@@ -334,6 +334,24 @@ int fsraft_softmax_rows_bwd(const float* A, float* dA, int64_t rows, int n, hipS
  * of dS = A * (dA - rowsum(dA * A)) in place (n <= 8160). */
 int fsraft_softmax_rows_rec(float* S, int64_t rows, int n, hipStream_t stream);
 int fsraft_softmax_rows_bwd_rec(const void* A_records, float* dA, int64_t rows, int n, hipStream_t stream);
+/* RelPosEmb.forward + Attention.forward with --position_only / --position_and_content, pytorch/core/gma.py:6-31, 62-74: the
+ * row softmax above with the relative-position logits added while the row is in LDS.  n = h * w; row r of S [rows][n] is query
+ * (x, y) = ((r % n) / w, (r % n) % w), so rows is a multiple of n; G [rows][ldg] (ldg >= 2h + 2w - 2) holds the query's scores
+ * against the stacked table slices, G = scale * q . [rel_height.weight[P-h : P+h-1] ; rel_width.weight[P-w : P+w-1]]^T, and
+ *   logit[r][u*w + v] = (content ? S[r][u*w + v] : 0) + G[r][u - x + h - 1] + G[r][(2h - 1) + v - y + w - 1].
+ * content == 0 (position_only): S is written without being read.  records != 0: the probabilities leave as records, as
+ * fsraft_softmax_rows_rec (n % 32 == 0, S 16-byte aligned), bit for bit the records of the dense result.
+ * Limits (FS_ERR_ARG beyond them; one row plus its h + w bias values in the 64 KB of LDS a launch gets without an opt-in, less
+ * 16 bytes of static reduction words): 4 * ceil4(n) + 4 * (h + w) <= 65520. */
+int fsraft_softmax_rows_pos(float* S, const float* G, int64_t ldg, int64_t rows, int n, int h, int w, int content, int records,
+                            hipStream_t stream);
+/* Its backward (autograd of gma.py:6-31, 62-74): dA <- dS = A * (dA - rowsum(dA * A)) in place (records != 0: A is read as
+ * records and dS written as records, as fsraft_softmax_rows_bwd_rec; A and dA 16-byte aligned, n % 32 == 0), and the gradient of
+ * G, every one of the ldg columns of a row written (no memset needed):
+ *   dG[r][u - x + h - 1] = sum_v dS[r][u*w + v],  dG[r][(2h - 1) + v - y + w - 1] = sum_u dS[r][u*w + v],  0 elsewhere,
+ * summed in a fixed order without atomics.  Limit: 8 * ceil4(n) + 4 * (h + w) <= 65520 (two rows and the h + w sums in LDS). */
+int fsraft_softmax_rows_pos_bwd(const void* A, float* dA, float* dG, int64_t ldg, int64_t rows, int n, int h, int w, int records,
+                                hipStream_t stream);
 /* Aggregate.forward, gma.py:113: dst = x + gamma[0] * y with gamma a device scalar (the nn.Parameter). */
 int fsraft_gma_mix_fwd(const float* x, int ldx, const float* y, int ldy, const float* gamma, float* dst, int ldd,
                        int64_t M, int C, hipStream_t stream);

@@ -6,5 +6,7 @@ Layout mirrors the reference's PyTorch tree so it drops in:
     flow_supervisor_amd.core.raft      RAFT (+ upsample_flow)             (pytorch/core/raft.py)
     flow_supervisor_amd.core.utils.utils  coords_grid, bilinear_sampler, upflow8, InputPadder
     flow_supervisor_amd.alt_cuda_corr  forward / backward                 (pytorch/alt_cuda_corr)
+    flow_supervisor_amd.evaluate       validate_chairs / _sintel / _kitti / _kitti2012, create_*_submission, FlowMetrics
+                                                                          (pytorch/evaluate.py)
 The compute lives in csrc/*.hip behind the C ABI of include/fsraft.h (libfsraft.so).
 """

@@ -1396,3 +1396,34 @@ def conv_small_dgrad(dy, w_oihw, dst, mask, B, H, W):
 def col_sum_v(v, out, scale=1.0):
     M = v.t.numel() // v.ld
     L.check(_lib().fsraft_col_sum(ctypes.c_void_p(v.ptr), v.ld, M, v.C, L.ptr(out), float(scale), L.stream()), "col_sum")
+
+
+# ------------------------------------------------------------------ validation metrics
+def flow_metrics_scratch_bytes(B, H, W):
+    n = _lib().fsraft_flow_metrics_scratch_bytes(B, H, W)
+    if n == 1:
+        raise RuntimeError(f"libfsraft: flow_metrics_scratch_bytes({B}, {H}, {W}) failed with status 1 (bad argument)")
+    return n
+
+
+def flow_metrics(pred, gt, valid, sample_stats, acc=None, scratch=None):
+    """fsraft_flow_metrics: pred, gt [B,2,H,W] and valid [B,H,W] (or None) fp32 with unit x stride, any other strides (the
+    un-padded view of a padded prediction is read in place); sample_stats [B,8] fp64 is overwritten, acc [8] fp64 (or None) is
+    accumulated into.  scratch: an fp64 tensor of at least flow_metrics_scratch_bytes(B, H, W) bytes (None: allocated here)."""
+    L.require_cuda_f32(pred, gt, valid)
+    B, C, H, W = pred.shape
+    if C != 2 or gt.shape != pred.shape or (valid is not None and valid.shape != (B, H, W)):
+        raise RuntimeError(f"flow_metrics: pred {tuple(pred.shape)}, gt {tuple(gt.shape)}, "
+                           f"valid {None if valid is None else tuple(valid.shape)}")
+    if W > 1 and any(t.stride(-1) != 1 for t in (pred, gt, valid) if t is not None):
+        raise RuntimeError("flow_metrics: pred, gt and valid need a unit x stride")
+    for t, shape in ((sample_stats, (B, 8)), (acc, (8,))):
+        if t is not None and (t.dtype != torch.float64 or t.shape != shape or not t.is_contiguous() or t.device != pred.device):
+            raise RuntimeError(f"flow_metrics: statistics must be contiguous fp64 {shape} tensors on {pred.device}")
+    if scratch is None:
+        scratch = torch.empty(flow_metrics_scratch_bytes(B, H, W) // 8, device=pred.device, dtype=torch.float64)
+    vs = (valid.stride(0), valid.stride(1)) if valid is not None else (0, 0)
+    L.check(_lib().fsraft_flow_metrics(L.ptr(pred), *pred.stride()[:3], L.ptr(gt), *gt.stride()[:3], L.ptr(valid), *vs, B, H, W,
+                                       L.ptr(sample_stats), L.ptr(acc), L.ptr(scratch), scratch.numel() * scratch.element_size(),
+                                       L.stream()), "flow_metrics")
+    return sample_stats

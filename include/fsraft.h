@@ -388,6 +388,26 @@ int fsraft_sequence_loss(const float* const* pred, float* const* dpred, const fl
  * landed point (float64 distances, as scipy's griddata(method="nearest")); all zero when nothing lands.  out != flow. */
 int fsraft_forward_interpolate(const float* flow, float* out, int H, int W, hipStream_t stream);
 
+/* ---- validation metrics (a step next to the path: pytorch/evaluate.py:117-124 validate_sintel / validate_chairs and
+ * :150-165 validate_kitti, which reduce on the host after a device -> host copy of every prediction) --------------------
+ * One pass over B predictions against ground truth.  pred, gt: [B][2][H][W] views, valid: [B][H][W] (NULL: every pixel is
+ * valid); strides in elements, the x stride is 1, nothing else is assumed (pred is typically InputPadder.unpad of a padded
+ * prediction: a 4-byte aligned base and a row stride other than W).  Per pixel, in the reference's fp32 with every operation
+ * rounded on its own: d = pred - gt, epe = sqrt(d0*d0 + d1*d1), mag = sqrt(g0*g0 + g1*g1); a pixel counts when
+ * valid >= 0.5; it is an outlier when epe > 3 && epe / mag > 0.05 (mag == 0 gives inf, as in the reference).  Sums are fp64.
+ *   sample_stats[b] (overwritten) = { n valid, sum epe, n(epe < 1), n(epe < 3), n(epe < 5), n outliers, 0, 0 }
+ *   acc (nullable, accumulated into in stream order, ascending b): acc[0..5] += sample_stats[b][0..5]; for a sample with a
+ *   valid pixel acc[6] += its mean epe (evaluate.py:158) and acc[7] += 1.
+ * No atomics: bit-identical from run to run, and sample b of a batch gives the bits it gives alone.  scratch: at least
+ * fsraft_flow_metrics_scratch_bytes(B, H, W) bytes, 8-byte aligned like sample_stats and acc; nothing to initialise.
+ * fsraft_flow_metrics_scratch_bytes returns the size (a multiple of 64), or FS_ERR_ARG (1) for B, H or W below 1 or
+ * H * W beyond 2^31 - 1. */
+int fsraft_flow_metrics_scratch_bytes(int B, int H, int W);
+int fsraft_flow_metrics(const float* pred, int64_t pred_bs, int64_t pred_cs, int64_t pred_rs,
+                        const float* gt, int64_t gt_bs, int64_t gt_cs, int64_t gt_rs,
+                        const float* valid, int64_t valid_bs, int64_t valid_rs, int B, int H, int W,
+                        double* sample_stats, double* acc, void* scratch, int64_t scratch_bytes, hipStream_t stream);
+
 /* Channels-last ([B][HW][C], C % 4 == 0, C <= 256) variants, for the encoder stages whose convolutions run on
  * fsraft_conv_forward.  sums/sumsq/s1/s2 and dsum_g/dsum_gx: [B * 8][C] partial rows (workgroups spread their atomics over
  * eight rows per sample: thousands of adds on the same C addresses serialise in L2 otherwise; dsum_*: the per-channel sums

@@ -28,8 +28,8 @@ __device__ __forceinline__ float block_reduce(float v, float* red) {
   return MAX ? fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// One workgroup per row, in place.  The row is read once from HBM (float4), held in LDS (n <= 16384)
-// and written once: 8 bytes per element.
+// One workgroup per row, in place.  The row is read once from HBM (float4), held in LDS (4 ceil4(n) bytes within
+// SOFTMAX_LDS_BYTES: n <= 16380) and written once: 8 bytes per element.
 __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S, int n) {
   extern __shared__ float row[];
   __shared__ float red[4];
@@ -55,7 +55,8 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(float* __restrict__ S
   for (int i = (n4 << 2) + threadIdx.x; i < n; i += 256) p[i] = row[i] * inv;
 }
 
-// dS = A * (dA - sum_j dA_j A_j), written over dA.  A and dA are read once (LDS keeps the row of dA*A inputs).
+// dS = A * (dA - sum_j dA_j A_j), written over dA.  A and dA are read once (LDS keeps the row of dA*A inputs: 8 ceil4(n) bytes
+// within SOFTMAX_LDS_BYTES, n <= 8188).
 __global__ __launch_bounds__(256) void softmax_rows_bwd_kernel(const float* __restrict__ A, float* __restrict__ dA, int n) {
   extern __shared__ float row[];          // [2][n]: A row, dA row
   __shared__ float red[4];
@@ -226,34 +227,44 @@ __global__ __launch_bounds__(256) void gma_mix_bwd_kernel(const float* __restric
   if (threadIdx.x == 0) atomicAdd(dgamma, acc);
 }
 
+// Dynamic LDS a softmax launch may ask for: the 64 KB a launch gets without an opt-in, less the kernels' 16 static bytes
+// (`red[4]`).  ONE budget for the four LDS kernels: the dense pair routes rows over it to the big kernels, the record pair
+// refuses them (n <= 16352 / 8160 are the largest multiples of 32 inside it).  ops.POS_LDS_LIMIT is the same number.
+constexpr size_t SOFTMAX_LDS_BYTES = 65536 - 4 * sizeof(float);
+inline size_t ceil4(int n) { return ((size_t)n + 3) & ~(size_t)3; }
+
 inline int grid_for(int64_t work) { int64_t g = (work + 255) / 256; return (int)(g < 1 ? 1 : g > 4096 ? 4096 : g); }
 
 }  // namespace
 
 extern "C" int fsraft_softmax_rows(float* S, int64_t rows, int n, hipStream_t s) {
   if (!S || rows < 1 || n < 1 || rows > 0x7fffffff) return FS_ERR_ARG;
-  if (n > 16384) hipLaunchKernelGGL(softmax_rows_big_kernel, dim3((unsigned)rows), dim3(256), 0, s, S, n);
-  else hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), (size_t)((n + 3) & ~3) * 4, s, S, n);
+  const size_t lds = ceil4(n) * 4;                   // last LDS row: n = 16380
+  if (lds > SOFTMAX_LDS_BYTES) hipLaunchKernelGGL(softmax_rows_big_kernel, dim3((unsigned)rows), dim3(256), 0, s, S, n);
+  else hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), lds, s, S, n);
   return fs_launch_status();
 }
 extern "C" int fsraft_softmax_rows_bwd(const float* A, float* dA, int64_t rows, int n, hipStream_t s) {
   if (!A || !dA || rows < 1 || n < 1 || rows > 0x7fffffff) return FS_ERR_ARG;
-  if (n > 8192) hipLaunchKernelGGL(softmax_rows_bwd_big_kernel, dim3((unsigned)rows), dim3(256), 0, s, A, dA, n);
-  else hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3((unsigned)rows), dim3(256), (size_t)((n + 3) & ~3) * 8, s, A, dA, n);
+  const size_t lds = ceil4(n) * 8;                   // last LDS row: n = 8188
+  if (lds > SOFTMAX_LDS_BYTES) hipLaunchKernelGGL(softmax_rows_bwd_big_kernel, dim3((unsigned)rows), dim3(256), 0, s, A, dA, n);
+  else hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3((unsigned)rows), dim3(256), lds, s, A, dA, n);
   return fs_launch_status();
 }
 // In place: fp32 logits [rows][n] -> softmax probabilities as records [rows][n / 32][32 hi | 32 lo] (n % 32 == 0, n <= 16352:
 // the row in dynamic LDS plus the kernel's static reduction words stay within 64 KB, the launch limit without an opt-in -- there
 // is no second copy of the logits to fall back to if a launch were refused).
 extern "C" int fsraft_softmax_rows_rec(float* S, int64_t rows, int n, hipStream_t s) {
-  if (!S || rows < 1 || n < 32 || (n % 32) || n > 16352 || rows > 0x7fffffff || ((uintptr_t)S % 16)) return FS_ERR_ARG;
+  if (!S || rows < 1 || n < 32 || (n % 32) || (size_t)n * 4 > SOFTMAX_LDS_BYTES || rows > 0x7fffffff || ((uintptr_t)S % 16))
+    return FS_ERR_ARG;
   hipLaunchKernelGGL(softmax_rows_rec_kernel, dim3((unsigned)rows), dim3(256), (size_t)n * 4, s, S, n);
   return fs_launch_status();
 }
 // A: records of fsraft_softmax_rows_rec; dA: fp32 gradient in, records of dS out (in place).  n % 32 == 0, n <= 8160 (two rows
 // in dynamic LDS + the static reduction words within 64 KB).
 extern "C" int fsraft_softmax_rows_bwd_rec(const void* A, float* dA, int64_t rows, int n, hipStream_t s) {
-  if (!A || !dA || rows < 1 || n < 32 || (n % 32) || n > 8160 || rows > 0x7fffffff || ((uintptr_t)A % 16) || ((uintptr_t)dA % 16))
+  if (!A || !dA || rows < 1 || n < 32 || (n % 32) || (size_t)n * 8 > SOFTMAX_LDS_BYTES || rows > 0x7fffffff ||
+      ((uintptr_t)A % 16) || ((uintptr_t)dA % 16))
     return FS_ERR_ARG;
   hipLaunchKernelGGL(softmax_rows_bwd_rec_kernel, dim3((unsigned)rows), dim3(256), (size_t)n * 8, s, (const char*)A, dA, n);
   return fs_launch_status();

@@ -708,7 +708,8 @@ def gemm_tn_raw(A, lda, sA, Bm, ldb, sB, C, ldc, sC, batch, M, N, K, alpha=1.0, 
 
 # ------------------------------------------------------------------ GMA (attention / aggregate)
 def softmax_rows_(S):
-    """In-place softmax over the last dimension of a contiguous tensor (gma.py:74)."""
+    """In-place softmax over the last dimension of a contiguous tensor (gma.py:74).  Rows whose 4 ceil4(n) bytes fit
+    POS_LDS_LIMIT (n <= 16380) are held in LDS; longer rows are re-read from global memory (the big kernel)."""
     L.require_cuda_f32(S)
     n = S.shape[-1]
     L.check(_lib().fsraft_softmax_rows(L.ptr(S), S.numel() // n, n, L.stream()), "softmax_rows")
@@ -716,7 +717,8 @@ def softmax_rows_(S):
 
 
 def softmax_rows_bwd_(A, dA):
-    """dA <- A * (dA - sum(dA * A, -1)) in place."""
+    """dA <- A * (dA - sum(dA * A, -1)) in place.  Rows of A and dA in LDS while 8 ceil4(n) bytes fit POS_LDS_LIMIT
+    (n <= 8188); longer rows -- N = 8192, a 512 x 1024 crop, is one -- on the big kernel."""
     L.require_cuda_f32(A, dA)
     n = A.shape[-1]
     L.check(_lib().fsraft_softmax_rows_bwd(L.ptr(A), L.ptr(dA), A.numel() // n, n, L.stream()), "softmax_rows_bwd")

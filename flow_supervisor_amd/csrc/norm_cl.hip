@@ -27,6 +27,22 @@ __device__ __forceinline__ int64_t cl_pix_off(int b, int p, int HW, int C, int s
   return (((int64_t)b * (HW >> 2) + (y >> 1) * (s2w >> 1) + (x >> 1)) * 4 + ((y & 1) * 2 + (x & 1))) * C;
 }
 
+// Sum of the lanes_p pixel lanes' partial sums (thread pl * c4n + cl holds lane pl of channel quad cl), left in lane 0: pairwise
+// halving.  (One thread adding its column up was a chain of up to 256 adds -- C = 4 -- whose roundings all point the same way on
+// a flat plane: 19 u relative on the mean of a constant plane, 29 u on its sum of squares, where pairwise sums stay within 1.)
+__device__ __forceinline__ void cl_reduce_lanes(f32x4 (*red)[256], int pl, int lanes_p, int c4n) {
+  __syncthreads();
+  for (int n = lanes_p; n > 1;) {
+    const int half = (n + 1) >> 1;
+    if (pl + half < n) {                                   // (the idle tail threads have pl == lanes_p: never)
+      red[0][threadIdx.x] += red[0][threadIdx.x + half * c4n];
+      red[1][threadIdx.x] += red[1][threadIdx.x + half * c4n];
+    }
+    __syncthreads();
+    n = half;
+  }
+}
+
 // sums[b][c] += sum_pix x, sumsq[b][c] += sum_pix x^2
 __global__ __launch_bounds__(256) void cl_stats_kernel(const float* __restrict__ x, float* __restrict__ sums,
                                                        float* __restrict__ sumsq, int HW, int C, int PIX_PER_WG) {
@@ -43,10 +59,9 @@ __global__ __launch_bounds__(256) void cl_stats_kernel(const float* __restrict__
       s += v; q += v * v;
     }
   red[0][threadIdx.x] = s; red[1][threadIdx.x] = q;
-  __syncthreads();
+  cl_reduce_lanes(red, pl, lanes_p, c4n);
   if (threadIdx.x < c4n) {
-    f32x4 ts = {0.f, 0.f, 0.f, 0.f}, tq = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < lanes_p; ++k) { ts += red[0][k * c4n + threadIdx.x]; tq += red[1][k * c4n + threadIdx.x]; }
+    const f32x4 ts = red[0][threadIdx.x], tq = red[1][threadIdx.x];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int o = (b * CL_NSLOT + (int)(blockIdx.x % CL_NSLOT)) * C + threadIdx.x * 4 + i;     // partial rows: see CL_NSLOT
@@ -141,10 +156,9 @@ __global__ __launch_bounds__(256) void cl_bwd_sums_kernel(const float* __restric
       if (MODE == 1) *reinterpret_cast<f32x4*>(dx + o) = dv;
     }
   red[0][threadIdx.x] = a1; red[1][threadIdx.x] = a2;
-  __syncthreads();
+  cl_reduce_lanes(red, pl, lanes_p, c4n);
   if (threadIdx.x < c4n) {
-    f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = {0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < lanes_p; ++k) { t1 += red[0][k * c4n + threadIdx.x]; t2 += red[1][k * c4n + threadIdx.x]; }
+    const f32x4 t1 = red[0][threadIdx.x], t2 = red[1][threadIdx.x];
     // MODE 1 sums over the whole batch: spread the workgroups over gridDim.y * NSLOT partial rows ([B * NSLOT][C],
     // summed by the caller) -- thousands of atomics on the same C addresses serialise in L2 otherwise
     const int base = (b * CL_NSLOT + (int)(blockIdx.x % CL_NSLOT)) * C + threadIdx.x * 4;
@@ -260,7 +274,7 @@ extern "C" int fsraft_inorm_relu_cl_bwd(const float* g, const float* x, const fl
 }
 extern "C" int fsraft_affine_relu_cl_fwd(const float* x, const float* res, const float* scale, const float* shift, float* y, int64_t M,
                                          int C, int relu, int HW, int s2d_w, hipStream_t s) {
-  if (!x || !scale || !shift || !y || M < 1 || C < 4 || C % 4 || (s2d_w && (HW < 4 || M % HW || !s2d_ok(HW, s2d_w)))) return FS_ERR_ARG;
+  if (!x || !scale || !shift || !y || M < 1 || !cl_ok(C) || (s2d_w && (HW < 4 || M % HW || !s2d_ok(HW, s2d_w)))) return FS_ERR_ARG;
   int64_t blocks = (M * (C / 4) + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(cl_affine_fwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, scale, shift, y, M, C, relu, res, HW > 0 ? HW : 1, s2d_w);

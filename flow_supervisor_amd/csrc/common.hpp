@@ -2,13 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// the library's own C ABI: every extern "C" definition is compiled against its declaration
+#include "fsraft.h"
+#include "fsraft_tuning.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#define FS_OK 0
-#define FS_ERR_ARG 1      // bad argument (null pointer, unsupported size)
-#define FS_ERR_LAUNCH 2   // hipGetLastError() after launch was not hipSuccess
+#define FS_OK FSRAFT_OK
+#define FS_ERR_ARG FSRAFT_ERR_ARG         // bad argument (null pointer, unsupported size)
+#define FS_ERR_LAUNCH FSRAFT_ERR_LAUNCH   // hipGetLastError() after launch was not hipSuccess
 
 static inline int fs_launch_status() {
   return hipGetLastError() == hipSuccess ? FS_OK : FS_ERR_LAUNCH;

@@ -16,45 +16,12 @@
 //   ZR: z = sigmoid(.), r = sigmoid(.), stores z, r and r*h          (update.py:27-29 / 46-48)
 //   Q : q = tanh(.), stores q and h' = (1-z)*h + z*q                 (update.py:29-31 / 48-50)
 //
-// The weight-gradient kernel is the transposed product  dWpk[co][k] += sum_m dY[m,co] * Xg[m,k]
-// with the pixel dimension split across workgroups and fp32 atomics into the packed layout.
-#include "gemm_core.hpp"
-#include "gemm_core_split.hpp"
-#include "gemm_rec.hpp"
-#include <cstddef>
-#include <type_traits>
+// This file: the forward / data-gradient kernels and their dispatcher.  The weight gradient (the transposed product
+// dWpk[co][k] += sum_m dY[m,co] * Xg[m,k]) is conv_wgrad.hip, the weight packers conv_pack.hip, the knobs conv_tuning.hip;
+// conv_common.hpp holds what they share.
+#include "conv_common.hpp"
 
 namespace {
-
-struct Src { const float* p; int C; int ld; };
-struct Dst { float* p; int64_t bs, ps, cs; int n0; int accumulate; };   // channels [n0, next n0)
-
-struct ConvArgs {
-  Src src[3]; int nsrc;
-  const float* wpk; int Ktot;
-  const float* bias;
-  int B, H, W, KH, KW, N;        // N = output channels of this GEMM
-  int PH, PW;                    // tap t reads pixel (y + t / KW - PH, x + t % KW - PW); KH / 2, KW / 2 unless overridden
-  Dst dst[3]; int ndst;
-  int relu; float alpha;
-  // GRU epilogues
-  const float* h; int ldh;
-  const float* z; int ldz;
-  float* aux1; int ld1;          // ZR: r*h     Q: q
-  float* aux2; int ld2;          // ZR: r
-  int hid;
-  const float* pre; int ldpre;   // GRU epilogues: per-pixel addend to the pre-activation, [M][ldpre] (NULL: none)
-  // plain epilogue, per destination: ReLU-backward mask.  After scaling / accumulation, column j of the destination
-  // range (j < maskc) is zeroed where rmask[m*ldmask + j] <= 0 -- the data gradient of a layer whose input came
-  // out of a ReLU leaves the kernel already masked, instead of a separate pass over the tensor.
-  const float* rmask[3]; int ldmask[3]; int maskc[3];
-  // InstanceNorm statistics of the OUTPUT from the epilogue (kernels whose tiles lie inside one image: conv_patch.inc, the halo
-  // kernel): st_sum / st_sq [B * st_slots][N] += column sums of the tile's results and of their squares (fsraft_conv_forward_stats)
-  float* st_sum; float* st_sq; int st_slots;
-  int swz;                       // 1: XCD-aware workgroup -> tile mapping (see tile_of_block)
-  int ksplit;                    // > 1: blockIdx.z owns a slice of the k-tiles and parks its RAW partial tile in a workspace (dst[0],
-                                 // rows z * M + m): the first pass of the split-K route for small M (conv_finish_kernel is the second)
-};
 
 // Workgroups are dealt to the 8 XCDs round-robin by linear id, and each XCD has its own L2.  With the plain
 // (x = N tile, y = M tile) mapping the N tiles of one M tile -- which read the same activation rows -- land on
@@ -67,24 +34,6 @@ __device__ __forceinline__ void tile_of_block(int swz, int& bx, int& by) {
   const int t = x * q + (x < r ? x : r) + (i >> 3);
   bx = t % nx; by = t / nx;
 }
-
-// Arguments of the buffer-addressed split kernels: ConvArgs plus one dword per k-tile, built on the host, that
-// says where the tile comes from -- bits 0..15: SGPR byte offset / 16 of (tap shift, channel chunk) inside the
-// source, 16..19: tap, 20..21: source, 22..27: channels left in the source from this chunk (1..32).  The kernel
-// reads it with one scalar load; without it the (source, tap, chunk) decode is two integer divisions per k-tile,
-// which the compiler can only do on the vector ALU (~50 instructions) even though the values are wave-uniform.
-// "Uniform" form (BUF = 2), used when all sources share one row pitch and lie within 2 GiB of each other: two dwords
-// per k-tile -- the complete SGPR byte offset from ONE base pointer (source delta + tap shift + channel chunk), and
-// tap | channels-left << 4.  One descriptor and one pitch for the whole k-loop: the per-tile scalar work shrinks from
-// ~30 instructions (source selects, 64-bit base arithmetic) to a two-dword load and two bit-field extracts.
-constexpr int KTAB_MAX = 512;
-struct ConvArgsT {
-  ConvArgs a;
-  const float* ubase; int uld;   // uniform form: biased base pointer and the common pitch (floats)
-  unsigned ktab[KTAB_MAX];
-};
-
-enum { EPI_PLAIN = 0, EPI_ZR = 2, EPI_Q = 3 };
 
 template <class Cfg>
 struct ConvALoader {
@@ -166,25 +115,7 @@ struct SplitConvALoader {                 // implicit-GEMM gather of fp32 activa
 // channel chunk, source) is wave-uniform and travels in the SGPR offset, and "outside the image / outside the
 // matrix" is expressed by pointing the lane offset past num_records, which makes the hardware return zeros.
 // That removes the 64-bit per-lane address arithmetic and the bounds compares (about 15 VALU per 16-byte chunk)
-// from the k-loop; what is left per chunk is one mask test and one select.
-#define FS_RSRC_FLAGS 0x00020000            // raw buffer, 32-bit data format (gfx9 family word 3)
-#define FS_OOB 0x80000000u                  // lane offset that always fails the num_records check
-
-__device__ __forceinline__ unsigned uni(unsigned v) { return __builtin_amdgcn_readfirstlane(v); }
-template <class T>
-__device__ __forceinline__ const T* uni_ptr(const T* p) {
-  const uint64_t u = reinterpret_cast<uint64_t>(p);
-  return reinterpret_cast<const T*>((uint64_t)uni((unsigned)(u >> 32)) << 32 | uni((unsigned)u));
-}
-// p and bytes must be wave-uniform; the readfirstlanes state that (a descriptor the compiler believes to be
-// divergent is wrapped in a waterfall loop around every load).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-  const uint64_t u = reinterpret_cast<uint64_t>(p);
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u), hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
-  void* q = reinterpret_cast<void*>((uint64_t)hi << 32 | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(q, 0, __builtin_amdgcn_readfirstlane(bytes), FS_RSRC_FLAGS);
-}
-
+// from the k-loop; what is left per chunk is one mask test and one select.  (FS_OOB, make_rsrc: conv_common.hpp)
 template <class Cfg>
 struct BufConvALoader {
   static constexpr int NCH = Cfg::NCH_A, NREG = NCH * 4;
@@ -911,702 +842,6 @@ int launch_halo(const HaloArgs& h, hipStream_t s) {
   return fs_launch_status();
 }
 
-
-// ---------------------------------------------------------------- weight gradient
-struct WgradArgs {
-  const float* dy; int ldy; int Cout;     // dY (already multiplied by act'), [M][ldy]
-  Src src[3]; int nsrc;
-  float* dwpk; int Ktot;
-  int B, H, W, KH, KW;
-  int kchunk;                              // pixels per split (multiple of 32)
-  float* dbias;                            // optional: dbias[co] += sum_pixels dY[pixel][co] (fused in the split kernel)
-  // XCD-aware launch (xcd_xt > 0): 1-D grid; the xcd_xt packed-K tiles that read the SAME dY tile -- one (Cout tile, pixel
-  // split) group -- get linear ids 8 apart, i.e. the same XCD and its L2, instead of being dealt round-robin over all 8.
-  int xcd_xt, xcd_yt, xcd_groups;
-};
-
-// Several (dY, X) pairs of identical shape in one launch -- the 12 iterations of a step: dW = sum_t dY_t^T X_t is one
-// reduction over 12 x M pixels, so the per-launch prologue / atomic epilogue is paid once per step instead of once
-// per iteration.  blockIdx.z = segment * zs + pixel split.  The pointer tables are read from the kernarg segment.
-constexpr int WGRAD_MAX_SEG = 16;
-struct WgradArgsM {
-  WgradArgs a;
-  int nseg, zs;
-  const float* dys[WGRAD_MAX_SEG];
-  const float* srcs[3][WGRAD_MAX_SEG];
-};
-
-template <class Cfg>
-struct ShiftedXLoader {                    // Bs[k = pixel][n = ci] <- X[pixel + off][ci0 + n]
-  static constexpr int BN = Cfg::BN, BK = Cfg::BK, LD = Cfg::LDB;
-  static constexpr int F4 = BN / 4;
-  static constexpr int NF4 = BK * F4 / 256;
-  static constexpr int NREG = NF4 * 4;
-  static constexpr int NCH = NF4;
-  const float* p; int ld, cvalid;          // p already offset by ci0; cvalid = channels left from ci0
-  int dy, dx, H, W, HW; int64_t M; int64_t m_begin, m_end;
-  __device__ __forceinline__ bool fetch_chunk(int kt, float (&r)[NREG], int j) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / F4, c4 = e % F4;
-    const int64_t m = m_begin + (int64_t)kt * BK + k;
-    const int64_t mm = m < m_end ? m : m_begin;
-    const int64_t b = mm / HW; const int pix = (int)(mm % HW);
-    const int yy = pix / W + dy, xx = pix % W + dx;
-    const bool ok = m < m_end && c4 * 4 < cvalid && yy >= 0 && yy < H && xx >= 0 && xx < W;
-    const f32x4 v = gload4(p + (ok ? (b * HW + (int64_t)yy * W + xx) * ld + c4 * 4 : 0));
-    r[4 * j + 0] = v[0]; r[4 * j + 1] = v[1]; r[4 * j + 2] = v[2]; r[4 * j + 3] = v[3];
-    return ok;
-  }
-  __device__ __forceinline__ void store_chunk(float* t, const float (&r)[NREG], int j, bool ok) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / F4, c4 = e % F4;
-    f32x4 v = {r[4 * j + 0], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]};
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    *reinterpret_cast<f32x4*>(t + k * LD + c4 * 4) = ok ? v : z;
-  }
-};
-
-template <class Cfg>
-struct DyLoader {                          // As[k = pixel][m = co] <- dY[pixel][co0 + m]
-  static constexpr int BM = Cfg::BM, BK = Cfg::BK, LD = Cfg::LDA;
-  static constexpr int F4 = BM / 4;
-  static constexpr int NF4 = BK * F4 / 256;
-  static constexpr int NREG = NF4 * 4;
-  static_assert((BK * F4) % 256 == 0, "dy tile must divide over 256 threads");
-  static constexpr int NCH = NF4;
-  const float* p; int ld, cvalid; int64_t m_begin, m_end;
-  __device__ __forceinline__ bool fetch_chunk(int kt, float (&r)[NREG], int j) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / F4, c4 = e % F4;
-    const int64_t m = m_begin + (int64_t)kt * BK + k;
-    const bool ok = m < m_end && c4 * 4 < cvalid;
-    const f32x4 v = gload4(p + (ok ? m * ld + c4 * 4 : 0));
-    r[4 * j + 0] = v[0]; r[4 * j + 1] = v[1]; r[4 * j + 2] = v[2]; r[4 * j + 3] = v[3];
-    return ok;
-  }
-  __device__ __forceinline__ void store_chunk(float* t, const float (&r)[NREG], int j, bool ok) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / F4, c4 = e % F4;
-    f32x4 v = {r[4 * j + 0], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]};
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    *reinterpret_cast<f32x4*>(t + k * LD + c4 * 4) = ok ? v : z;
-  }
-};
-
-// ---- split-bf16 weight gradient (k-major operands, transposed LDS reads) ---------------------
-template <class Cfg>
-struct SplitDyLoader {                    // chunk e: pixel k = e / 32, channels 4*(e % 32) .. +3 of the 128-wide co tile
-  static constexpr int NCH = Cfg::NCH_A, NREG = NCH * 4;
-  const float* p; int ld, cvalid; int64_t m_begin, m_end;
-  __device__ __forceinline__ void fetch_chunk(int kt, float (&r)[NREG], int j) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / (Cfg::BM / 4), c4 = e % (Cfg::BM / 4);
-    const int64_t m = m_begin + (int64_t)kt * 32 + k;
-    const bool ok = m < m_end && c4 * 4 < cvalid;
-    const f32x4 v = gload4(ok ? p + m * ld + c4 * 4 : g_fsraft_zero16);
-    r[4 * j + 0] = v[0]; r[4 * j + 1] = v[1]; r[4 * j + 2] = v[2]; r[4 * j + 3] = v[3];
-  }
-};
-template <class Cfg>
-struct SplitShiftedXLoader {
-  static constexpr int NCH = Cfg::NCH_B, NREG = NCH * 4;
-  const float* p; int ld, cvalid;
-  int dy, dx, H, W, HW; int64_t m_begin, m_end;
-  __device__ __forceinline__ void fetch_chunk(int kt, float (&r)[NREG], int j) const {
-    const int e = threadIdx.x + 256 * j;
-    const int k = e / (Cfg::BN / 4), c4 = e % (Cfg::BN / 4);
-    const int64_t m = m_begin + (int64_t)kt * 32 + k;
-    const int64_t mm = m < m_end ? m : m_begin;
-    const int pix = (int)(mm % HW);
-    const int yy = pix / W + dy, xx = pix % W + dx;
-    const bool ok = m < m_end && c4 * 4 < cvalid && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W;
-    const f32x4 v = gload4(ok ? p + (mm + dy * W + dx) * ld + c4 * 4 : g_fsraft_zero16);
-    r[4 * j + 0] = v[0]; r[4 * j + 1] = v[1]; r[4 * j + 2] = v[2]; r[4 * j + 3] = v[3];
-  }
-};
-
-// buffer-addressed variants of the two loaders above (see BufConvALoader): per-lane offsets are fixed for the whole
-// k-loop, the k-tile advance is one SGPR offset, and the "shifted pixel inside the image" test -- three integer
-// divisions per 16-byte chunk in the loaders above, ~300 VALU instructions per k-tile -- is a bit test against a
-// per-workgroup pixel mask that is computed once (one word per k-tile, in LDS).
-constexpr int WGRAD_MASK_WORDS = 2048;     // pixels per workgroup / 32 (host caps the pixel split at 65536)
-template <class Cfg>
-struct BufDyLoader {
-  static constexpr int NCH = Cfg::NCH_A, NREG = NCH * 4;
-  const float* base; unsigned ld4; int npix;
-  unsigned voff[NCH]; int krow[NCH];
-  __device__ __forceinline__ void fetch_tile(int kt, float (&r)[NREG]) const {
-    const int ku = __builtin_amdgcn_readfirstlane(kt);
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, 0x7fffffffu);
-    const unsigned soff = (unsigned)ku * 32u * ld4;
-    const int left = npix - ku * 32;                              // rows of this tile that exist
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const unsigned voffj = voff[j] | (krow[j] < left ? 0u : FS_OOB);
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voffj, soff, 0);
-      const f32x4 f = __builtin_bit_cast(f32x4, v);
-      r[4 * j + 0] = f[0]; r[4 * j + 1] = f[1]; r[4 * j + 2] = f[2]; r[4 * j + 3] = f[3];
-    }
-  }
-};
-template <class Cfg>
-struct BufShiftedXLoader {
-  static constexpr int NCH = Cfg::NCH_B, NREG = NCH * 4;
-  const float* base; unsigned ld4; const unsigned* mask;       // mask: LDS, bit k of word kt = pixel mb + 32 kt + k usable
-  unsigned voff[NCH]; int krow[NCH];
-  __device__ __forceinline__ void fetch_tile(int kt, float (&r)[NREG]) const {
-    const int ku = __builtin_amdgcn_readfirstlane(kt);
-    const unsigned w = __builtin_amdgcn_readfirstlane(mask[ku]);
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, 0x7fffffffu);
-    const unsigned soff = (unsigned)ku * 32u * ld4;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const unsigned voffj = voff[j] | ((__builtin_amdgcn_ubfe(w, (unsigned)krow[j], 1u) ^ 1u) << 31);
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voffj, soff, 0);
-      const f32x4 f = __builtin_bit_cast(f32x4, v);
-      r[4 * j + 0] = f[0]; r[4 * j + 1] = f[1]; r[4 * j + 2] = f[2]; r[4 * j + 3] = f[3];
-    }
-  }
-};
-
-using SWCfg128 = SplitTnCfg<128, 128, 2, 2, 2>;
-using SWCfg128S = SplitTnCfg<128, 128, 2, 2, 1>;
-using SWCfg128W8 = SplitTnCfg<128, 128, 2, 4, 1, 512>;   // eight waves per workgroup (multi-segment launches)
-
-template <class Cfg, bool BUF = false, bool MULTI = false>
-__global__ __launch_bounds__(Cfg::NT) void conv_wgrad_split_kernel(const std::conditional_t<MULTI, WgradArgsM, WgradArgs> args) {
-  static_assert(Cfg::NT == 256 || BUF, "512-thread workgroups use the buffer-addressed loaders");
-  __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS_BYTES];
-  __shared__ unsigned pixmask[BUF ? WGRAD_MASK_WORDS : 1];
-  const WgradArgs& a = [&]() -> const WgradArgs& { if constexpr (MULTI) return args.a; else return args; }();
-  int bx = blockIdx.x, by = blockIdx.y, zblock = blockIdx.z, seg = 0;
-  if (a.xcd_xt > 0) {
-    const int span = 8 * a.xcd_xt, r = blockIdx.x / span, rem = blockIdx.x - r * span;
-    const int g = r * 8 + (rem & 7);
-    if (g >= a.xcd_groups) return;
-    if (a.xcd_yt > 0) { bx = rem >> 3; by = g % a.xcd_yt; zblock = g / a.xcd_yt; }        // group = (Cout tile, pixel split)
-    else { const int tile = rem >> 3, x0 = -a.xcd_yt; bx = tile % x0; by = tile / x0; zblock = g; }   // group = pixel split
-  }
-  if constexpr (MULTI) { seg = zblock / args.zs; zblock -= seg * args.zs; seg = __builtin_amdgcn_readfirstlane(seg); }
-  const int HW = a.H * a.W;
-  const int64_t M = (int64_t)a.B * HW;
-  const int taps = a.KH * a.KW;
-  int t = bx, s = 0, kofs = 0;
-  for (;; ++s) {
-    const int ct = (a.src[s].C + Cfg::BN - 1) / Cfg::BN;
-    if (t < taps * ct) break;
-    t -= taps * ct;
-    kofs += taps * ((a.src[s].C + 31) / 32) * 32;
-  }
-  Src sc = s == 0 ? a.src[0] : s == 1 ? a.src[1] : a.src[2];
-  const float* dyp = a.dy;
-  if constexpr (MULTI) {       // this segment's tensors, read from the kernarg tables with a uniform index
-    typedef const float* fptr;
-    const auto* karg = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
-    dyp = ((const fptr __attribute__((address_space(4)))*)(karg + offsetof(WgradArgsM, dys)))[seg];
-    sc.p = ((const fptr __attribute__((address_space(4)))*)(karg + offsetof(WgradArgsM, srcs)))[s * WGRAD_MAX_SEG + seg];
-  }
-  const int ct = (sc.C + Cfg::BN - 1) / Cfg::BN;
-  const int tap = t / ct, ci0 = (t % ct) * Cfg::BN;
-  const int cpad = ((sc.C + 31) / 32) * 32;
-  kofs += tap * cpad + ci0;
-  const int co0 = by * Cfg::BM;
-  const int64_t mb = (int64_t)zblock * a.kchunk;
-  const int64_t me = mb + a.kchunk < M ? mb + a.kchunk : M;
-  if (mb >= M) return;
-  const int coleft = ((a.Cout + 3) / 4) * 4 - co0;     // dy may be a channel slice of a wider buffer: never read past it
-  const int cleft = ((sc.C + 3) / 4) * 4 - ci0;
-  const int dyy = tap / a.KW - a.KH / 2, dxx = tap % a.KW - a.KW / 2;
-  const int KT = (int)((me - mb + 31) / 32);
-  f32x16 acc[Cfg::TM][Cfg::TN];
-#pragma unroll
-  for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float colsum[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool want_bias = a.dbias != nullptr && bx == 0;        // one x-tile per (co tile, pixel split) owns the bias
-  if constexpr (BUF) {
-    // pixel mask: bit k of word w <=> pixel mb + 32 w + k exists and its (dy, dx)-shifted neighbour is inside the image
-    for (int i = threadIdx.x; i < KT * 32; i += Cfg::NT) {
-      const int64_t m = mb + i;
-      bool ok = m < me;
-      if (ok) {
-        const int pix = (int)(m % HW), yy = pix / a.W + dyy, xx = pix % a.W + dxx;
-        ok = (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-      }
-      const unsigned long long bal = __ballot(ok);
-      if ((threadIdx.x & 63) == 0) { pixmask[i >> 5] = (unsigned)bal; pixmask[(i >> 5) + 1] = (unsigned)(bal >> 32); }
-    }
-    __syncthreads();
-    BufDyLoader<Cfg> la;
-    la.base = uni_ptr(dyp + co0 + mb * a.ldy); la.ld4 = uni((unsigned)a.ldy * 4u); la.npix = (int)(me - mb);
-    const int cva = coleft < Cfg::BM ? coleft : Cfg::BM;
-#pragma unroll
-    for (int j = 0; j < BufDyLoader<Cfg>::NCH; ++j) {
-      const int e = threadIdx.x + Cfg::NT * j, k = e / (Cfg::BM / 4), c4 = e % (Cfg::BM / 4);
-      la.krow[j] = k; la.voff[j] = c4 * 4 < cva ? (unsigned)(k * a.ldy + c4 * 4) * 4u : FS_OOB;
-    }
-    BufShiftedXLoader<Cfg> lb;
-    lb.base = uni_ptr(sc.p + ci0 + (mb + dyy * a.W + dxx) * sc.ld); lb.ld4 = uni((unsigned)sc.ld * 4u); lb.mask = pixmask;
-    const int cvb = cleft < Cfg::BN ? cleft : Cfg::BN;
-#pragma unroll
-    for (int j = 0; j < BufShiftedXLoader<Cfg>::NCH; ++j) {
-      const int e = threadIdx.x + Cfg::NT * j, k = e / (Cfg::BN / 4), c4 = e % (Cfg::BN / 4);
-      lb.krow[j] = k; lb.voff[j] = c4 * 4 < cvb ? (unsigned)(k * sc.ld + c4 * 4) * 4u : FS_OOB;
-    }
-    if (want_bias) split_mainloop_tn<Cfg, BufDyLoader<Cfg>, BufShiftedXLoader<Cfg>, true>(lds, KT, la, lb, acc, colsum);
-    else split_mainloop_tn<Cfg>(lds, KT, la, lb, acc);
-  } else {
-  SplitDyLoader<Cfg> la{dyp + co0, a.ldy, coleft < Cfg::BM ? coleft : Cfg::BM, mb, me};
-  SplitShiftedXLoader<Cfg> lb{sc.p + ci0, sc.ld, cleft < Cfg::BN ? cleft : Cfg::BN, dyy, dxx, a.H, a.W, HW, mb, me};
-  if (want_bias) split_mainloop_tn<Cfg, SplitDyLoader<Cfg>, SplitShiftedXLoader<Cfg>, true>(lds, KT, la, lb, acc, colsum);
-  else split_mainloop_tn<Cfg>(lds, KT, la, lb, acc);
-  }
-  if (want_bias) {
-    // this thread's columns are co0 + 4*(tid % 32) .. +3; NT/32 threads (tid / 32) share them
-    float* part = reinterpret_cast<float*>(lds);
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) part[(threadIdx.x >> 5) * Cfg::BM + 4 * (threadIdx.x & 31) + q] = colsum[q];
-    __syncthreads();
-    if (threadIdx.x < Cfg::BM) {
-      float s = 0.f;
-#pragma unroll
-      for (int g = 0; g < Cfg::NT / 32; ++g) s += part[g * Cfg::BM + threadIdx.x];
-      if (co0 + threadIdx.x < a.Cout) atomicAdd(a.dbias + co0 + threadIdx.x, s);
-    }
-  }
-#pragma unroll
-  for (int nt = 0; nt < Cfg::TN; ++nt) {
-    const int n = acc_col<Cfg>(nt);
-    if (ci0 + n >= cpad) continue;
-#pragma unroll
-    for (int mt = 0; mt < Cfg::TM; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + acc_row<Cfg>(mt, r);
-        if (co < a.Cout) atomicAdd(a.dwpk + (int64_t)co * a.Ktot + kofs + n, acc[mt][nt][r]);
-      }
-  }
-}
-
-// ---- few-channel layers (encoder residual stages, C = 32 / 64 / 96) -----------------------------------------------
-// A 128-column x tile holding one tap of a 64-channel source is half empty, and so is a 128-row dY tile of a 64-channel
-// output: the kernel above then spends 4x the useful MFMA work.  Here the x tile packs TP = BN / cpad CONSECUTIVE taps
-// side by side (the packed-K layout is tap-major, so the tile's columns are one contiguous run of dW columns) and the
-// dY tile is 64 wide.  A lane's chunk belongs to one tap for the whole k-loop: the tap's pixel shift is folded into its
-// fixed buffer offset and its "neighbour inside the image" bit comes from that tap's own pixel mask.
-constexpr int WGRAD_PACK_WORDS = 256;      // pixel-mask words per tap slot (pixel split <= 32 * 254)
-constexpr int WGRAD_PACK_SLOTS = 8;
-using SWCfgPack = SplitTnCfg<64, 192, 2, 2, 1>;
-
-template <class Cfg>
-struct BufPackedXLoader {
-  static constexpr int NCH = Cfg::NCH_B, NREG = NCH * 4;
-  const float* base; unsigned ld4; const unsigned* mask;       // mask[word * SLOTS + slot]
-  unsigned voff[NCH]; int krow[NCH]; int slot[NCH];
-  __device__ __forceinline__ void fetch_tile(int kt, float (&r)[NREG]) const {
-    const int ku = __builtin_amdgcn_readfirstlane(kt);
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(base, 0x7fffffffu);
-    const unsigned soff = (unsigned)ku * 32u * ld4;
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) {
-      const unsigned w = mask[ku * WGRAD_PACK_SLOTS + slot[j]];
-      const unsigned voffj = voff[j] | ((__builtin_amdgcn_ubfe(w, (unsigned)krow[j], 1u) ^ 1u) << 31);
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voffj, soff, 0);
-      const f32x4 f = __builtin_bit_cast(f32x4, v);
-      r[4 * j + 0] = f[0]; r[4 * j + 1] = f[1]; r[4 * j + 2] = f[2]; r[4 * j + 3] = f[3];
-    }
-  }
-};
-
-// grid: x = tap group, y = 64-row Cout tile, z = pixel split.  Single source, split-bf16 arithmetic.
-template <class Cfg>
-__global__ __launch_bounds__(Cfg::NT) void conv_wgrad_pack_kernel(const WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) char lds[Cfg::LDS_BYTES];
-  __shared__ unsigned pixmask[WGRAD_PACK_WORDS * WGRAD_PACK_SLOTS];
-  const int HW = a.H * a.W;
-  const int64_t M = (int64_t)a.B * HW;
-  const int taps = a.KH * a.KW;
-  const Src sc = a.src[0];
-  const int cpad = ((sc.C + 31) / 32) * 32;
-  int TP = Cfg::BN / cpad;
-  if (TP > WGRAD_PACK_SLOTS) TP = WGRAD_PACK_SLOTS;
-  int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  if (a.xcd_xt > 0) {          // tap groups of one (Cout tile, pixel split) on one XCD: they read the same dY and x rows
-    const int span = 8 * a.xcd_xt, r = blockIdx.x / span, rem = blockIdx.x - r * span;
-    const int g = r * 8 + (rem & 7);
-    if (g >= a.xcd_groups) return;
-    bx = rem >> 3; by = g % a.xcd_yt; bz = g / a.xcd_yt;
-  }
-  const int tap0 = bx * TP;
-  const int ntap = taps - tap0 < TP ? taps - tap0 : TP;
-  const int kofs = tap0 * cpad;
-  const int co0 = by * Cfg::BM;
-  const int64_t mb = (int64_t)bz * a.kchunk;
-  const int64_t me = mb + a.kchunk < M ? mb + a.kchunk : M;
-  if (mb >= M) return;
-  const int coleft = ((a.Cout + 3) / 4) * 4 - co0;
-  const int cva = coleft < Cfg::BM ? coleft : Cfg::BM;
-  const int cvb = ((sc.C + 3) / 4) * 4;
-  const int KT = (int)((me - mb + 31) / 32);
-  f32x16 acc[Cfg::TM][Cfg::TN];
-#pragma unroll
-  for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  float colsum[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool want_bias = a.dbias != nullptr && bx == 0;
-  // pixel masks, one per tap slot: bit k of word w <=> pixel mb + 32 w + k exists and its shifted neighbour is inside the image
-  for (int i = threadIdx.x; i < KT * 32; i += Cfg::NT) {
-    const int64_t m = mb + i;
-    const int pix = (int)(m % HW), py = pix / a.W, px = pix % a.W;
-    for (int tp = 0; tp < ntap; ++tp) {
-      const int tap = tap0 + tp;
-      const int yy = py + tap / a.KW - a.KH / 2, xx = px + tap % a.KW - a.KW / 2;
-      const bool ok = m < me && (unsigned)yy < (unsigned)a.H && (unsigned)xx < (unsigned)a.W;
-      const unsigned long long bal = __ballot(ok);
-      if ((threadIdx.x & 63) == 0) {
-        pixmask[(i >> 5) * WGRAD_PACK_SLOTS + tp] = (unsigned)bal;
-        pixmask[((i >> 5) + 1) * WGRAD_PACK_SLOTS + tp] = (unsigned)(bal >> 32);
-      }
-    }
-  }
-  __syncthreads();
-  BufDyLoader<Cfg> la;
-  la.base = uni_ptr(a.dy + co0 + mb * a.ldy); la.ld4 = uni((unsigned)a.ldy * 4u); la.npix = (int)(me - mb);
-#pragma unroll
-  for (int j = 0; j < BufDyLoader<Cfg>::NCH; ++j) {
-    const int e = threadIdx.x + Cfg::NT * j, k = e / (Cfg::BM / 4), c4 = e % (Cfg::BM / 4);
-    la.krow[j] = k; la.voff[j] = c4 * 4 < cva ? (unsigned)(k * a.ldy + c4 * 4) * 4u : FS_OOB;
-  }
-  // taps ascend in (dy, dx), so the group's first tap has the smallest pixel shift: every lane offset is >= 0
-  const int shift0 = (tap0 / a.KW - a.KH / 2) * a.W + (tap0 % a.KW - a.KW / 2);
-  BufPackedXLoader<Cfg> lb;
-  lb.base = uni_ptr(sc.p + (mb + shift0) * sc.ld); lb.ld4 = uni((unsigned)sc.ld * 4u); lb.mask = pixmask;
-#pragma unroll
-  for (int j = 0; j < BufPackedXLoader<Cfg>::NCH; ++j) {
-    const int e = threadIdx.x + Cfg::NT * j, k = e / (Cfg::BN / 4), col = (e % (Cfg::BN / 4)) * 4;
-    const int tp = col / cpad, cc = col - tp * cpad, tap = tap0 + tp;
-    const int shift = (tap / a.KW - a.KH / 2) * a.W + (tap % a.KW - a.KW / 2) - shift0;
-    const bool valid = tp < ntap && cc < cvb;
-    lb.krow[j] = k; lb.slot[j] = valid ? tp : 0;
-    lb.voff[j] = valid ? (unsigned)((k + shift) * sc.ld + cc) * 4u : FS_OOB;
-  }
-  if (want_bias) split_mainloop_tn<Cfg, BufDyLoader<Cfg>, BufPackedXLoader<Cfg>, true>(lds, KT, la, lb, acc, colsum);
-  else split_mainloop_tn<Cfg>(lds, KT, la, lb, acc);
-  if (want_bias) {
-    // this thread's dY columns are co0 + 4*(tid % (BM/4)) .. +3; NT / (BM/4) threads share them
-    constexpr int Q = Cfg::BM / 4, G = Cfg::NT / Q;
-    float* part = reinterpret_cast<float*>(lds);
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) part[(threadIdx.x / Q) * Cfg::BM + 4 * (threadIdx.x % Q) + q] = colsum[q];
-    __syncthreads();
-    if (threadIdx.x < Cfg::BM) {
-      float s = 0.f;
-#pragma unroll
-      for (int g = 0; g < G; ++g) s += part[g * Cfg::BM + threadIdx.x];
-      if (co0 + threadIdx.x < a.Cout) atomicAdd(a.dbias + co0 + threadIdx.x, s);
-    }
-  }
-#pragma unroll
-  for (int nt = 0; nt < Cfg::TN; ++nt) {
-    const int n = acc_col<Cfg>(nt);
-    if (n >= ntap * cpad) continue;
-#pragma unroll
-    for (int mt = 0; mt < Cfg::TM; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + acc_row<Cfg>(mt, r);
-        if (co < a.Cout) atomicAdd(a.dwpk + (int64_t)co * a.Ktot + kofs + n, acc[mt][nt][r]);
-      }
-  }
-}
-
-// grid: x = packed-K tile (source, tap, 128-channel tile), y = Cout tile, z = pixel split
-template <class Cfg>
-__global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
-  __shared__ __attribute__((aligned(16))) float lds[Cfg::LDS_FLOATS];
-  const int HW = a.H * a.W;
-  const int64_t M = (int64_t)a.B * HW;
-  const int taps = a.KH * a.KW;
-  // decode blockIdx.x -> (source, tap, channel tile)
-  int t = blockIdx.x, s = 0, kofs = 0;
-  for (;; ++s) {
-    const int ct = (a.src[s].C + Cfg::BN - 1) / Cfg::BN;
-    if (t < taps * ct) break;
-    t -= taps * ct;
-    kofs += taps * ((a.src[s].C + 31) / 32) * 32;
-  }
-  const Src sc = s == 0 ? a.src[0] : s == 1 ? a.src[1] : a.src[2];
-  const int ct = (sc.C + Cfg::BN - 1) / Cfg::BN;
-  const int tap = t / ct, ci0 = (t % ct) * Cfg::BN;
-  const int cpad = ((sc.C + 31) / 32) * 32;
-  kofs += tap * cpad + ci0;
-  const int co0 = blockIdx.y * Cfg::BM;
-  const int64_t mb = (int64_t)blockIdx.z * a.kchunk;
-  const int64_t me = mb + a.kchunk < M ? mb + a.kchunk : M;
-  if (mb >= M) return;
-
-  const int coleft = ((a.Cout + 3) / 4) * 4 - co0;     // dy may be a channel slice of a wider buffer: never read past it
-  DyLoader<Cfg> la{a.dy + co0, a.ldy, coleft < Cfg::BM ? coleft : Cfg::BM, mb, me};
-  const int cleft = ((sc.C + 3) / 4) * 4 - ci0;
-  ShiftedXLoader<Cfg> lb{sc.p + ci0, sc.ld, cleft < Cfg::BN ? cleft : Cfg::BN,
-                         tap / a.KW - a.KH / 2, tap % a.KW - a.KW / 2, a.H, a.W, HW, M, mb, me};
-
-  f32x16 acc[Cfg::TM][Cfg::TN];
-#pragma unroll
-  for (int i = 0; i < Cfg::TM; ++i)
-#pragma unroll
-    for (int j = 0; j < Cfg::TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  gemm_mainloop<Cfg>(lds, (int)((me - mb + Cfg::BK - 1) / Cfg::BK), la, lb, acc);
-
-#pragma unroll
-  for (int nt = 0; nt < Cfg::TN; ++nt) {
-    const int n = acc_col<Cfg>(nt);
-    if (ci0 + n >= cpad) continue;
-#pragma unroll
-    for (int mt = 0; mt < Cfg::TM; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = co0 + acc_row<Cfg>(mt, r);
-        if (co < a.Cout) atomicAdd(a.dwpk + (int64_t)co * a.Ktot + kofs + n, acc[mt][nt][r]);
-      }
-  }
-}
-
-// ---------------------------------------------------------------- weight (un)packing
-// mode 0 (forward):  wpk[n][k(s,t,c)] = W[n][coff_s + c][t]                       n < Cout
-// mode 1 (dgrad):    wpk[n][k(t',c)]  = W[c][n][taps-1-t']                        n < Cin_total, c < Cout
-// mode 2 (unpack dW): W[n][coff_s + c][t] (+)= wpk[n][k(s,t,c)]   (inverse of mode 0)
-struct PackArgs {
-  float* w;            // OIHW [Cout][Cin][KH*KW]
-  float* wpk;
-  int Cout, Cin, taps;
-  int C[3]; int nsrc;  // forward source split of Cin (mode 0/2); ignored for mode 1
-  int Ktot, rows;
-  int mode, accumulate;
-  int split;           // modes 0/1: write [32 hi | 32 lo] bf16 records instead of fp32 (same byte size)
-};
-
-__device__ __forceinline__ void store_packed(const PackArgs& a, int64_t e, float v) {
-  if (!a.split) { a.wpk[e] = v; return; }
-  // element e = n*Ktot + k  ->  record (e / 32) of 64 shorts: hi at [k % 32], lo at [32 + k % 32]
-  const __bf16 h = (__bf16)v;
-  const __bf16 l = (__bf16)(v - (float)h);
-  __bf16* rec = reinterpret_cast<__bf16*>(a.wpk) + (e >> 5) * 64;
-  rec[e & 31] = h;
-  rec[32 + (e & 31)] = l;
-}
-
-__global__ __launch_bounds__(256) void pack_weight_kernel(PackArgs a) {
-  const int64_t total = (int64_t)a.rows * a.Ktot;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int n = (int)(e / a.Ktot);
-    int k = (int)(e % a.Ktot);
-    if (a.mode == 1) {
-      const int cpad = ((a.Cout + 31) / 32) * 32;
-      const int tp = k / cpad, c = k % cpad;
-      float v = 0.f;
-      if (c < a.Cout && n < a.Cin) v = a.w[((int64_t)c * a.Cin + n) * a.taps + (a.taps - 1 - tp)];
-      store_packed(a, e, v);
-    } else {
-      int s = 0, coff = 0;
-      for (; s < a.nsrc; ++s) {
-        const int span = a.taps * (((a.C[s] + 31) / 32) * 32);
-        if (k < span) break;
-        k -= span; coff += a.C[s];
-      }
-      const int cpad = ((a.C[s] + 31) / 32) * 32;
-      const int t = k / cpad, c = k % cpad;
-      const bool ok = c < a.C[s] && n < a.Cout;
-      if (a.mode == 0) {
-        store_packed(a, e, ok ? a.w[((int64_t)n * a.Cin + coff + c) * a.taps + t] : 0.f);
-      } else if (ok) {
-        float* d = a.w + ((int64_t)n * a.Cin + coff + c) * a.taps + t;
-        *d = a.accumulate ? *d + a.wpk[e] : a.wpk[e];
-      }
-    }
-  }
-}
-
-// ---- batched packing: every GEMM-ready weight image of a module (and, in reverse, every weight gradient) in one launch ----
-// One job = one packed matrix.  Its logical OIHW weight is read in place from the parameter tensors: up to three tensors
-// stacked along the output channels (fused layers: z|r gates, flow-head|mask-head), GEMM sources = channel ranges of the
-// parameters' input channels (a GRU convolution split into its (h, motion) part and its context part), optionally seen
-// through the space-to-depth rewrite of a stride-2 3x3 weight.  (Mirror of fsraft_pack_job in include/fsraft.h.)
-struct PackJob {
-  float* w[3]; int rows[3]; int npiece;
-  float* wpk;
-  int cin_full, kh, kw;
-  int srcC[3], srcOff[3], nsrc;
-  int mode, flags;
-  float scale; int accumulate;
-};
-constexpr int PACK_JOBS = 16;
-struct PackJobs { PackJob j[PACK_JOBS]; };
-
-// logical element (output channel n, concatenated-source channel given as (source s, channel c), tap t of kh x kw) -> address
-// in the parameter tensors, or nullptr where the logical weight is structurally zero (space-to-depth slots)
-__device__ __forceinline__ float* pack_elem(const PackJob& j, int n, int s, int c, int t) {
-  int p = 0;
-  while (p + 1 < j.npiece && n >= j.rows[p]) { n -= j.rows[p]; ++p; }
-  float* w = j.w[p];
-  if (j.flags & 2) {
-    // parameter [N][C][3][3] (stride 2, pad 1); logical [N][4C][2][2]: channel (sy*2+sx)*C + c0, tap (ty, tx);
-    // input row 2y - 1 + ky = 2(y + ty - 1) + sy  ->  ky = 2*ty + sy - 1
-    const int C = j.cin_full;
-    const int sp = c / C, c0 = c % C;
-    const int ky = 2 * (t >> 1) + (sp >> 1) - 1, kx = 2 * (t & 1) + (sp & 1) - 1;
-    if (ky < 0 || kx < 0) return nullptr;
-    return w + ((int64_t)n * C + c0) * 9 + ky * 3 + kx;
-  }
-  return w + ((int64_t)n * j.cin_full + j.srcOff[s] + c) * (j.kh * j.kw) + t;
-}
-
-__device__ __forceinline__ void pack_store(const PackJob& j, int Ktot, int rows, int n, int k, float v) {
-  const int64_t e = (int64_t)n * Ktot + k;
-  if (j.mode < 10) { j.wpk[e] = v; return; }
-  const __bf16 h = (__bf16)v;
-  const __bf16 l = (__bf16)(v - (float)h);
-  __bf16* out = reinterpret_cast<__bf16*>(j.wpk);
-  if (!(j.flags & 1)) {
-    __bf16* rec = out + (e >> 5) * 64;
-    rec[e & 31] = h;
-    rec[32 + (e & 31)] = l;
-    return;
-  }
-  // fragment order (resident-patch kernel): [k-tile][32-row block][hi/lo][k quarter pair s][k half][row][4 dwords];
-  // bf16 q of a record's 32-k run sits in dword q / 2: s = q / 16, k half = (q / 8) % 2, dword = (q / 2) % 4
-  const int nb = (rows + 31) / 32, kt = k >> 5, q = k & 31;
-  const int64_t base = (((int64_t)kt * nb + (n >> 5)) * 2) ;
-  const int sidx = (q >> 4) & 1, kh2 = (q >> 3) & 1, dw = (q >> 1) & 3, half = q & 1;
-  const int64_t dh = ((((base + 0) * 2 + sidx) * 2 + kh2) * 32 + (n & 31)) * 4 + dw;
-  const int64_t dl = ((((base + 1) * 2 + sidx) * 2 + kh2) * 32 + (n & 31)) * 4 + dw;
-  out[dh * 2 + half] = h;
-  out[dl * 2 + half] = l;
-}
-
-__global__ __launch_bounds__(256) void pack_jobs_kernel(PackJobs tab) {
-  const PackJob& j = tab.j[blockIdx.y];
-  const int taps = j.kh * j.kw;
-  int cout = 0;
-  for (int p = 0; p < j.npiece; ++p) cout += j.rows[p];
-  if (j.mode == 3) {                         // concatenated bias vectors
-    for (int e = blockIdx.x * 256 + threadIdx.x; e < cout; e += gridDim.x * 256) {
-      int n = e, p = 0;
-      while (p + 1 < j.npiece && n >= j.rows[p]) { n -= j.rows[p]; ++p; }
-      j.wpk[e] = j.w[p][n];
-    }
-    return;
-  }
-  int cin = 0;
-  for (int s = 0; s < j.nsrc; ++s) cin += j.srcC[s];
-  const int m = j.mode % 10;
-  int Ktot, rows;
-  if (m == 1) { Ktot = taps * ((cout + 31) / 32 * 32); rows = cin; }
-  else { Ktot = 0; for (int s = 0; s < j.nsrc; ++s) Ktot += taps * ((j.srcC[s] + 31) / 32 * 32); rows = cout; }
-  const int rows_out = (j.flags & 1) ? (rows + 31) / 32 * 32 : rows;     // fragment order pads the rows with zeros
-  const int64_t total = (int64_t)rows_out * Ktot;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int n = (int)(e / Ktot);
-    int k = (int)(e % Ktot);
-    if (m == 1) {
-      const int cpad = (cout + 31) / 32 * 32;
-      const int tp = k / cpad, c = k % cpad;
-      float v = 0.f;
-      if (c < cout && n < rows) {
-        int s = 0, cs = n;
-        while (s + 1 < j.nsrc && cs >= j.srcC[s]) { cs -= j.srcC[s]; ++s; }
-        const float* q = pack_elem(j, c, s, cs, taps - 1 - tp);
-        if (q) v = *q;
-      }
-      pack_store(j, Ktot, rows, n, k, v);
-    } else {
-      const int k0 = k;
-      int s = 0;
-      for (; s < j.nsrc; ++s) {
-        const int span = taps * ((j.srcC[s] + 31) / 32 * 32);
-        if (k < span) break;
-        k -= span;
-      }
-      const int cpad = (j.srcC[s] + 31) / 32 * 32;
-      const int t = k / cpad, c = k % cpad;
-      const bool ok = c < j.srcC[s] && n < rows;
-      float* q = ok ? pack_elem(j, n, s, c, t) : nullptr;
-      if (m == 0) pack_store(j, Ktot, rows, n, k0, q ? *q : 0.f);
-      else if (q) *q = j.accumulate ? *q + j.scale * j.wpk[e] : j.scale * j.wpk[e];
-    }
-  }
-}
-
-using Cfg128 = GemmCfg<128, 128, 32, 2, 2, 2, 2>;
-using Cfg64 = GemmCfg<128, 64, 32, 4, 1, 2, 2>;
-using CfgM64 = GemmCfg<64, 128, 32, 1, 4, 2, 2>;     // half-height tile: doubles the workgroup count for narrow N
-using Cfg6464 = GemmCfg<64, 64, 32, 2, 2, 2, 2>;     // small tile: 4 workgroups/CU, fine-grained balance over 256 CUs
-using WCfg6464 = GemmCfg<64, 64, 32, 2, 2, 0, 0>;
-using Cfg6464K16 = GemmCfg<64, 64, 16, 2, 2, 2, 2>;  // 17 KB of LDS: 8 workgroups/CU
-using CfgM64K16 = GemmCfg<64, 128, 16, 1, 4, 2, 2>;  // 25 KB: 6 workgroups/CU
-
-using SCfg128 = SplitCfg<128, 128, 2, 2>;
-using SCfgN256 = SplitCfg<64, 256, 1, 4, 2, true>;   // 80 KB of LDS: two workgroups per CU; each wave owns 64x64, A rows are read once for N = 256
-using SCfg256W16 = SplitCfg<256, 128, 4, 4, 2, true, 1024>;  // sixteen waves, one workgroup per CU
-using SCfg128W8 = SplitCfg<128, 128, 2, 4, 2, true, 512>;   // eight waves per workgroup, 66 KB of LDS: two workgroups per CU
-using SCfg256N64 = SplitCfg<256, 64, 4, 2, 2, true, 512>;   // N <= 64 layers at large M (encoder layer1, f2): a 128-wide tile would be half empty
-using SCfgM64 = SplitCfg<64, 128, 1, 4, 2, true>;    // swizzled 128-byte rows: 48 KB of LDS -> three workgroups per CU
-int g_wgrad_split = 2;  // 0: exact fp32; 1/2: split-bf16 weight gradient (double / single LDS image)   (key 4)
-int g_wgrad_w8 = 0;       // 512-thread workgroups in the multi-segment weight gradient (key 15); measured slower (7.96 vs 7.32 ms/step): its grid is large already
-int g_conv_w8 = 1;        // 512-thread 128x128 tiles for wide layers (key 13); g_conv_w8_min: minimum workgroup count (key 14)
-int g_conv_w8_min = 64;      // (measured faster than 64x128 four-wave tiles on every update-block shape, N = 64 .. 576)
-int g_conv_uniform = 1;   // uniform-pitch k-tile table when the sources allow it (key 12)
-int g_wgrad_blocks_multi = 2048;   // workgroup target of the multi-segment launch (key 11); measured 512: 9.0, 1024: 8.5, 2048: 8.35 ms/step
-int g_wgrad_multi = 1;  // one weight-gradient launch per layer per step over all stashed iterations (key 10)
-int g_conv_n256 = 0;    // 64x256 tiles for layers whose N fills them (key 9); measured slower than 64x128 (zr 139 vs 119 us, hd 182 vs 125 us)
-int g_wgrad_buf = 1;    // buffer-addressed loaders + pixel mask in the split weight-gradient kernel (key 8)
-int g_xcd_swizzle = 0;  // experiment switch (key 7)
-int g_conv_buf = 1;     // buffer-addressed loaders in the split conv kernels (key 5): 0 never, 1 on 64-row tiles, 2 always
-int g_conv_split = 1;   // 0: exact fp32 MFMA; 1: split-bf16 (3-MFMA) core for forward / data-gradient convolutions (key 3)
-int g_conv_tile = 0;    // 0 auto, 1 force 128x128, 2 force 64x128, 3 force 64x64   (fsraft_set_tuning key 0)
-int g_wgrad_tile = 0;   // 0 auto (128x128), 3 force 64x64                           (key 1)
-int g_conv_n64 = 1;            // 256x64 tiles for N <= 64 (key 18) once M reaches g_conv_n64_min_m (key 19)
-int g_conv_n64_min_m = 65536;
-int g_conv_halo = 1;           // resident-patch 3x3 kernel for few-channel layers at large M (key 20; threshold key 21)
-int g_conv_halo_min_m = 65536;
-int g_wgrad_xcd = 1;           // XCD-aware workgroup order in the multi-segment weight gradient (key 22; 2: the few-channel kernel too).
-                               // Measured: 10.73 -> 9.72 ms/step of weight-gradient time (15 K-tiles re-read each dY tile)
-int g_wgrad_patch = 1;         // resident-pixel-block weight gradient for the 3x3 / 1x5 / 5x1 layers (wgrad_patch.inc, key 27)
-int g_wgrad_pack = 1;          // few-channel single-source layers on conv_wgrad_pack_kernel (key 16)
-int g_wgrad_patch1 = 8192;     // single-segment 3x3 layers with at least this many pixels on the resident-block kernel (key 29; 0: never)
-int g_wgrad_blocks_pack = 1024;   // its workgroup target (key 17)
-int g_wgrad_blocks = 512;   // target workgroup count of the pixel split (key 2); measured 256: 12.9, 512: 11.5, 1024: 12.9, 2048: 14.1 ms/step
-using Cfg32 = GemmCfg<128, 32, 32, 4, 1, 2, 2>;
-// weight-gradient tiles: LDS images are filled with float4 rows, so pitches stay multiples of 4
-using WCfg128 = GemmCfg<128, 128, 32, 2, 2, 0, 0>;
-using WCfg32 = GemmCfg<32, 128, 32, 1, 4, 0, 0>;
-
-// Route attestation (fsraft_conv_last_route, include/fsraft_tuning.h): every launch site records which kernel the calling
-// thread's last forward / data-gradient call (t_route[0]) and weight-gradient call (t_route[1]) ran.  Codes as in the header.
-thread_local int t_route[2] = {0, 0};
-template <class Cfg>
-constexpr int route_gemm() {
-  return std::is_same_v<Cfg, Cfg32> ? 1 : std::is_same_v<Cfg, Cfg64> ? 2 : std::is_same_v<Cfg, CfgM64> ? 3 :
-         std::is_same_v<Cfg, Cfg128> ? 4 : std::is_same_v<Cfg, Cfg6464> ? 5 : std::is_same_v<Cfg, Cfg6464K16> ? 6 :
-         std::is_same_v<Cfg, CfgM64K16> ? 7 : 0;
-}
-template <class Cfg>
-constexpr int route_split() {
-  return std::is_same_v<Cfg, SCfgN256> ? 30 : std::is_same_v<Cfg, SCfg256N64> ? 31 : std::is_same_v<Cfg, SCfg256W16> ? 32 :
-         std::is_same_v<Cfg, SCfg128W8> ? 33 : std::is_same_v<Cfg, SCfgM64> ? 34 : std::is_same_v<Cfg, SCfg128> ? 35 : 0;
-}
-
 // Fills the per-k-tile table of the buffer-addressed kernels; false when the shape does not fit its fields
 // (more than KTAB_MAX k-tiles, more than 15 taps, tap/channel offsets beyond 1 MiB, tensors of 2 GiB or more).
 bool build_ktab(const ConvArgs& a, ConvArgsT& t) {
@@ -1635,7 +870,7 @@ bool build_ktab(const ConvArgs& a, ConvArgsT& t) {
 bool build_ktab_uniform(const ConvArgs& a, ConvArgsT& t) {
   const int taps = a.KH * a.KW, KT = a.Ktot / 32, PH = a.PH, PW = a.PW;
   const int64_t M = (int64_t)a.B * a.H * a.W;
-  if (!g_conv_uniform || 2 * KT > KTAB_MAX || taps > 15) return false;
+  if (!knob.conv_uniform || 2 * KT > KTAB_MAX || taps > 15) return false;
   const int ld = a.src[0].ld;
   const float* lo = a.src[0].p;
   for (int s = 0; s < a.nsrc; ++s) {
@@ -1742,7 +977,6 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(const ConvArgs a, cons
   }
 }
 
-int g_conv_ksplit = -1;          // -1 auto (small grids only), 0 / 1 off, >= 2 forced slice count (fsraft_set_tuning key 32)
 // Split-K scratch: the ABI allocates nothing, the caller lends it -- per CALL (fsraft_conv_desc.ws, what the Python mirror does) or,
 // for bindings written against the round-3 header, per calling THREAD (fsraft_conv_workspace).  Both live in thread_local storage,
 // so two host threads enqueueing convolutions for two devices / streams (the reference's nn.DataParallel caller,
@@ -1763,9 +997,9 @@ thread_local int64_t g_conv_ws_floats = 0;
 // at 1 x 47x156: 47 -> 41 us, but the 20-tile data gradient 1x5 128 -> 256: 23 -> 29); above ~120 tiles nothing gains.
 int pick_ksplit(int64_t tiles, int KT, int N, int64_t M, int ldw, int bm) {
   int S = 1;
-  if (g_conv_ksplit >= 2) S = g_conv_ksplit;
-  else if (g_conv_ksplit == -1 && bm == 64 && tiles <= 150 && N <= 256 && KT >= 16) S = (int)((400 + tiles - 1) / tiles);
-  else if (g_conv_ksplit == -1 && bm == 128 && tiles <= 120 && N <= 256 && KT >= (N <= 128 ? 36 : 48)) S = tiles <= 115 ? (int)(230 / tiles) : 2;
+  if (knob.conv_ksplit >= 2) S = knob.conv_ksplit;
+  else if (knob.conv_ksplit == -1 && bm == 64 && tiles <= 150 && N <= 256 && KT >= 16) S = (int)((400 + tiles - 1) / tiles);
+  else if (knob.conv_ksplit == -1 && bm == 128 && tiles <= 120 && N <= 256 && KT >= (N <= 128 ? 36 : 48)) S = tiles <= 115 ? (int)(230 / tiles) : 2;
   if (S > KT / 6) S = KT / 6;
   if (S > 6) S = 6;
   while (S > 1 && (int64_t)S * M * ldw > g_conv_ws_floats) --S;
@@ -1783,14 +1017,14 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
   ConvArgsT t;
   // XCD-aware tile order (tile_of_block) once several N tiles re-read each A tile and the grid is many rounds deep:
   // 192 -> 256 at M = 225 K (encoder-sized data gradients): 776 -> 714 us; nothing at the update block's 220..880 tiles.
-  const int swz = g_xcd_swizzle || (grid.x >= 2 && (int64_t)grid.x * grid.y >= 2048);
+  const int swz = knob.xcd_swizzle || (grid.x >= 2 && (int64_t)grid.x * grid.y >= 2048);
   // buffer-addressed loaders + branch-free k-loop: measured faster on the 64-row tiles, slower on 128x128
-  const bool buf = g_conv_buf == 2 || (g_conv_buf == 1 && Cfg::BM == 64) || Cfg::BN == 256 || Cfg::NT != 256;
+  const bool buf = knob.conv_buf == 2 || (knob.conv_buf == 1 && Cfg::BM == 64) || Cfg::BN == 256 || Cfg::NT != 256;
   if constexpr (Cfg::LDS_ALLOC >= Cfg::BM * (Cfg::BN + 4) * 4) {
     // split-K route (small M): partial tiles into the workspace, then conv_finish_kernel with the layer's own epilogue
     const int ldw = (a.N + 3) / 4 * 4;
     const bool gru_ok = epi == EPI_PLAIN || (a.N % 4 == 0 && (!a.pre || a.ldpre % 4 == 0));
-    const int S = (buf && g_conv_ws && gru_ok && (Cfg::BM == 64 || (Cfg::BM == 128 && Cfg::NT == 512) || g_conv_ksplit >= 2)) ? pick_ksplit((int64_t)grid.x * grid.y, a.Ktot / 32, a.N, M, ldw, Cfg::BM) : 1;
+    const int S = (buf && g_conv_ws && gru_ok && (Cfg::BM == 64 || (Cfg::BM == 128 && Cfg::NT == 512) || knob.conv_ksplit >= 2)) ? pick_ksplit((int64_t)grid.x * grid.y, a.Ktot / 32, a.N, M, ldw, Cfg::BM) : 1;
     if (S > 1) {
       const bool uni_tab = build_ktab_uniform(a, t);
       if (uni_tab || build_ktab(a, t)) {
@@ -1809,9 +1043,7 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
         if (rc) return rc;
         const int64_t work = (int64_t)M * (ldw / 4);
         const int fb = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-        if (epi == EPI_PLAIN) hipLaunchKernelGGL(conv_finish_kernel<EPI_PLAIN>, dim3(fb), dim3(256), 0, s, a, g_conv_ws, S, ldw);
-        else if (epi == EPI_ZR) hipLaunchKernelGGL(conv_finish_kernel<EPI_ZR>, dim3(fb), dim3(256), 0, s, a, g_conv_ws, S, ldw);
-        else hipLaunchKernelGGL(conv_finish_kernel<EPI_Q>, dim3(fb), dim3(256), 0, s, a, g_conv_ws, S, ldw);
+        with_epi(epi, [&](auto e) { hipLaunchKernelGGL(conv_finish_kernel<decltype(e)::value>, dim3(fb), dim3(256), 0, s, a, g_conv_ws, S, ldw); });
         return fs_launch_status();
       }
     }
@@ -1819,26 +1051,20 @@ int launch_conv_split(const ConvArgs& a, int epi, hipStream_t s) {
   if (buf && build_ktab_uniform(a, t)) {
     t.a.swz = swz;
     t_route[0] = route_split<Cfg>();
-    if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 2>), grid, dim3(Cfg::NT), 0, s, t);
-    else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR, 2>), grid, dim3(Cfg::NT), 0, s, t);
-    else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q, 2>), grid, dim3(Cfg::NT), 0, s, t);
+    with_epi(epi, [&](auto e) { hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, decltype(e)::value, 2>), grid, dim3(Cfg::NT), 0, s, t); });
     return fs_launch_status();
   }
   if (buf && build_ktab(a, t)) {
     t.a.swz = swz;
     t_route[0] = route_split<Cfg>();
-    if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN, 1>), grid, dim3(Cfg::NT), 0, s, t);
-    else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR, 1>), grid, dim3(Cfg::NT), 0, s, t);
-    else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q, 1>), grid, dim3(Cfg::NT), 0, s, t);
+    with_epi(epi, [&](auto e) { hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, decltype(e)::value, 1>), grid, dim3(Cfg::NT), 0, s, t); });
     return fs_launch_status();
   }
   if constexpr (Cfg::NT != 256) {
     return -1;          // the wide configurations exist for the buffer-addressed paths only: caller falls back
   } else {
   t_route[0] = route_split<Cfg>();
-  if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_PLAIN>), grid, dim3(256), 0, s, a);
-  else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_ZR>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, EPI_Q>), grid, dim3(256), 0, s, a);
+  with_epi(epi, [&](auto e) { hipLaunchKernelGGL((conv_igemm_split_kernel<Cfg, decltype(e)::value>), grid, dim3(256), 0, s, a); });
   return fs_launch_status();
   }
 }
@@ -1867,45 +1093,13 @@ int launch_conv(const ConvArgs& a, int epi, hipStream_t s) {
   const int M = a.B * a.H * a.W;
   dim3 grid(ceil_div(a.N, Cfg::BN), ceil_div(M, Cfg::BM));
   t_route[0] = route_gemm<Cfg>();
-  if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_PLAIN>), grid, dim3(256), 0, s, a);
-  else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_ZR>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((conv_igemm_kernel<Cfg, EPI_Q>), grid, dim3(256), 0, s, a);
+  with_epi(epi, [&](auto e) { hipLaunchKernelGGL((conv_igemm_kernel<Cfg, decltype(e)::value>), grid, dim3(256), 0, s, a); });
   return fs_launch_status();
 }
 
-int g_conv_patch_min_m = 8192;   // ... from this many pixels on (key 31)
-int g_conv_patch = 1;      // resident-patch, channel-streaming kernel for the 3x3 / 1x5 / 5x1 layers (conv_patch.inc, key 26; 2: 128-pixel tiles too)
-int g_conv_patch64 = 1;    // ... also for the 3x3 layers with 33..64 outputs (64-column tiles; key 28; 2: 128-pixel tiles)
 #include "conv_patch.inc"
 
-int conv_ktot(const int* C, int nsrc, int taps) {
-  int k = 0;
-  for (int s = 0; s < nsrc; ++s) k += taps * (((C[s] + 31) / 32) * 32);
-  return k;
-}
-
 }  // namespace
-
-// Flat C descriptor so the ABI stays plain-old-data (mirrored by ctypes in _lib.py).
-struct fsraft_conv_desc {
-  const float* src[3]; int srcC[3]; int srcld[3]; int nsrc;
-  const float* wpk; const float* bias;
-  const float* wpk_split;        // same matrix packed with mode 10/11 (or NULL): enables the split-bf16 core
-  int B, H, W, KH, KW, N;
-  float* dst[3]; int64_t dst_bs[3]; int64_t dst_ps[3]; int64_t dst_cs[3]; int dst_n0[3]; int dst_acc[3]; int ndst;
-  int relu; float alpha;
-  int epi;                       // 0 plain, 2 GRU z/r, 3 GRU q
-  const float* h; int ldh;
-  const float* z; int ldz;
-  float* aux1; int ld1;
-  float* aux2; int ld2;
-  int hid;
-  const float* pre; int ldpre;   // GRU epilogues: addend to the pre-activation (e.g. the context part of the conv), or NULL
-  const float* rmask[3]; int ldmask[3]; int maskc[3];   // epi 0, per destination: zero column j < maskc where rmask[m*ldmask+j] <= 0
-  const float* wpk_frag;         // wpk_split in fragment order (or NULL): enables the resident-patch 3x3 kernel
-  int pad_h1, pad_w1;            // 0: taps centred (KH / 2, KW / 2); else 1 + the top / left padding (even kernel sizes)
-  float* ws; int64_t ws_floats;  // split-K scratch of THIS call (NULL: the calling thread's fsraft_conv_workspace registration)
-};
 
 extern "C" int fsraft_conv_ktot(const int* srcC, int nsrc, int KH, int KW) {
   if (!srcC || nsrc < 1 || nsrc > 3) return -1;
@@ -1917,6 +1111,10 @@ namespace {
 // carry the statistics pick it up and say so
 struct StatReq { float* sum; float* sq; int slots; bool done; };
 thread_local StatReq t_stat{nullptr, nullptr, 0, false};
+template <class Args>                      // ConvArgs or HaloArgs
+void attach_stats(Args& p, bool want) {
+  if (want) { p.st_sum = t_stat.sum; p.st_sq = t_stat.sq; p.st_slots = t_stat.slots; }
+}
 }  // namespace
 
 extern "C" int fsraft_conv_forward(const fsraft_conv_desc* d, hipStream_t stream) {
@@ -1929,10 +1127,8 @@ extern "C" int fsraft_conv_forward(const fsraft_conv_desc* d, hipStream_t stream
   g_conv_ws = d->ws ? d->ws : t_reg_ws;                     // scratch of THIS call (thread_local: see the declaration)
   g_conv_ws_floats = d->ws ? d->ws_floats : t_reg_ws_floats;
   ConvArgs a{};
-  for (int s = 0; s < 3; ++s) {
-    a.src[s] = Src{s < d->nsrc ? d->src[s] : d->src[0], s < d->nsrc ? d->srcC[s] : 0, s < d->nsrc ? d->srcld[s] : 4};
-    if (s < d->nsrc && (!d->src[s] || d->srcld[s] % 4 != 0 || d->srcC[s] < 1)) return FS_ERR_ARG;
-  }
+  if (!fill_srcs(a.src, d->src, d->srcC, d->srcld, d->nsrc)) return FS_ERR_ARG;
+  for (int s = 0; s < d->nsrc; ++s) if (d->srcC[s] < 1) return FS_ERR_ARG;
   a.nsrc = d->nsrc;
   a.wpk = d->wpk; a.Ktot = conv_ktot(d->srcC, d->nsrc, d->KH * d->KW); a.bias = d->bias;
   a.B = d->B; a.H = d->H; a.W = d->W; a.KH = d->KH; a.KW = d->KW; a.N = d->N;
@@ -1953,79 +1149,78 @@ extern "C" int fsraft_conv_forward(const fsraft_conv_desc* d, hipStream_t stream
     a.rmask[i] = on ? d->rmask[i] : nullptr; a.ldmask[i] = d->ldmask[i]; a.maskc[i] = d->maskc[i];
     if (on && (d->ldmask[i] % 4 != 0 || ((uintptr_t)d->rmask[i] & 15))) return FS_ERR_ARG;
   }
-  a.swz = g_xcd_swizzle;
+  a.swz = knob.xcd_swizzle;
   if (d->epi == EPI_ZR && (!d->h || !d->aux1 || !d->aux2 || d->hid * 2 != d->N)) return FS_ERR_ARG;
   if (d->epi == EPI_Q && (!d->h || !d->z || !d->aux1)) return FS_ERR_ARG;
   if (d->epi != EPI_PLAIN && d->epi != EPI_ZR && d->epi != EPI_Q) return FS_ERR_ARG;
-  if (g_conv_patch && g_conv_patch64 && g_conv_split == 1 && d->wpk_split && d->epi == EPI_PLAIN && d->KH == 3 && d->KW == 3 &&
-      d->N > 32 && d->N <= 64 && (int64_t)d->B * d->H * d->W >= g_conv_patch_min_m) {
+  if (knob.conv_patch && knob.conv_patch64 && knob.conv_split == 1 && d->wpk_split && d->epi == EPI_PLAIN && d->KH == 3 && d->KW == 3 &&
+      d->N > 32 && d->N <= 64 && (int64_t)d->B * d->H * d->W >= knob.conv_patch_min_m) {
     ConvArgs p = a;
     p.wpk = d->wpk_split;
-    if (want_stats) { p.st_sum = t_stat.sum; p.st_sq = t_stat.sq; p.st_slots = t_stat.slots; }
+    attach_stats(p, want_stats);
     const int rc = launch_conv_patch(p, d->epi, stream);
     if (rc >= 0) { t_stat.done = want_stats; return rc; }
   }
-  if (g_conv_halo && g_conv_split == 1 && d->wpk_frag && d->epi == EPI_PLAIN && d->nsrc == 1 && d->KH == 3 && d->KW == 3 &&
+  if (knob.conv_halo && knob.conv_split == 1 && d->wpk_frag && d->epi == EPI_PLAIN && d->nsrc == 1 && d->KH == 3 && d->KW == 3 &&
       a.PH == 1 && a.PW == 1 &&
       d->srcC[0] % 4 == 0 && d->srcC[0] > 32 && d->srcC[0] <= 64 && d->N <= 128 && d->N > 32 && d->ndst == 1 &&
       d->dst_cs[0] == 1 && d->dst_n0[0] == 0 && !(d->dst_acc[0] && d->relu) && !a.rmask[0] && d->alpha == 1.0f &&
-      (int64_t)d->B * d->H * d->W >= g_conv_halo_min_m && (int64_t)d->H * d->W * d->srcld[0] * 4 < 0x7fffffff) {
+      (int64_t)d->B * d->H * d->W >= knob.conv_halo_min_m && (int64_t)d->H * d->W * d->srcld[0] * 4 < 0x7fffffff) {
     HaloArgs h{d->src[0], d->srcld[0], d->srcC[0], reinterpret_cast<const char*>(d->wpk_frag), d->bias,
                d->dst[0], d->dst_bs[0], d->dst_ps[0], d->N, d->B, d->H, d->W, d->relu, d->dst_acc[0], nullptr, nullptr, 0};
-    bool halo_stats = false;
     // Measured (scripts/conv_micro.py, halo on / off): 64 -> 64 at 8x220x512 238 vs 442 us.  With three or four channel
     // groups the patch takes 78 / 104 KB of LDS, one or two 4-wave workgroups per CU, and the kernel loses to the implicit
     // GEMM (96 -> 96 at 8x110x256: 249 vs 165 us; 128 -> 128 at 8x55x128: 93 vs 65 us), so only two-group layers come here.
-    if (want_stats) { h.st_sum = t_stat.sum; h.st_sq = t_stat.sq; h.st_slots = t_stat.slots; halo_stats = true; }
-    t_stat.done = halo_stats;
+    attach_stats(h, want_stats);
+    t_stat.done = want_stats;
     t_route[0] = d->N > 64 ? 21 : 20;
     return d->N > 64 ? launch_halo<2, 2>(h, stream) : launch_halo<2, 1>(h, stream);
   }
   if (d->N <= 32 && d->epi == EPI_PLAIN) return launch_conv<Cfg32>(a, d->epi, stream);
   // 33..64 outputs: half of a 64x128 split tile is padding, still ~2x faster than the exact 64-wide kernel
-  if (d->N <= 64 && d->epi == EPI_PLAIN && !(g_conv_split && d->wpk_split && g_conv_buf)) return launch_conv<Cfg64>(a, d->epi, stream);
+  if (d->N <= 64 && d->epi == EPI_PLAIN && !(knob.conv_split && d->wpk_split && knob.conv_buf)) return launch_conv<Cfg64>(a, d->epi, stream);
   // one workgroup per CU is not enough to keep the matrix pipe busy: when the 128x128 grid has
   // fewer than ~2 workgroups per CU, halve the tile height
   const int M = d->B * d->H * d->W;
-  if (g_conv_split && d->wpk_split && d->N > 32) {
+  if (knob.conv_split && d->wpk_split && d->N > 32) {
     a.wpk = d->wpk_split;
     // 64x128 tiles with the buffer-addressed loaders and the branch-free k-loop are the fastest variant on every
     // update-block shape at M = 28160 (scripts/conv_micro.py: zr 129 us, hd 142 us, q 65 us, m2 61 us, c1 41 us;
     // the 128x128 kernel needs 131 / 157 / 87 / 78 / 45 us); 128x128 stays selectable (key 3 = 4) and is the
     // fallback for shapes the k-tile table cannot describe.
-    const bool narrow = g_conv_buf != 0 || (int64_t)ceil_div(d->N, 128) * ceil_div(M, 128) < 400;
-    if (g_conv_patch && g_conv_split == 1 && d->KH * d->KW > 1 && d->N > 64 && M >= g_conv_patch_min_m) {
+    const bool narrow = knob.conv_buf != 0 || (int64_t)ceil_div(d->N, 128) * ceil_div(M, 128) < 400;
+    if (knob.conv_patch && knob.conv_split == 1 && d->KH * d->KW > 1 && d->N > 64 && M >= knob.conv_patch_min_m) {
       ConvArgs p = a;
-      if (want_stats) { p.st_sum = t_stat.sum; p.st_sq = t_stat.sq; p.st_slots = t_stat.slots; }
+      attach_stats(p, want_stats);
       const int rc = launch_conv_patch(p, d->epi, stream);
       if (rc >= 0) { t_stat.done = want_stats; return rc; }
     }
-    if (g_conv_split == 5 || (g_conv_split == 1 && g_conv_n256 && d->N >= 256 &&
+    if (knob.conv_split == 5 || (knob.conv_split == 1 && knob.conv_n256 && d->N >= 256 &&
                               ceil_div(d->N, 256) * 256 <= ceil_div(d->N, 128) * 128))
       return launch_conv_split<SCfgN256>(a, d->epi, stream);
-    if (g_conv_split == 1 && g_conv_n64 && d->N <= 64 && d->epi == EPI_PLAIN && M >= g_conv_n64_min_m) {
+    if (knob.conv_split == 1 && knob.conv_n64 && d->N <= 64 && d->epi == EPI_PLAIN && M >= knob.conv_n64_min_m) {
       const int rc = launch_conv_split_plain<SCfg256N64>(a, stream);
       if (rc >= 0) return rc;
     }
     // eight-wave 128x128 tiles where they fill the machine in one round (N >= 256 at M ~ 28 K): key 13
     // sixteen-wave 256x128 tiles: a further 3-6 % on the 192..512-output layers (zr 93 -> 87 us), slower on m2 (N = 576)
-    if (g_conv_split == 1 && ((g_conv_w8 == 1 && d->N >= 192 && d->N <= 512 && M >= 16384) || g_conv_w8 == 2) && d->N >= 192) {
+    if (knob.conv_split == 1 && ((knob.conv_w8 == 1 && d->N >= 192 && d->N <= 512 && M >= 16384) || knob.conv_w8 == 2) && d->N >= 192) {
       const int rc = launch_conv_split<SCfg256W16>(a, d->epi, stream);
       if (rc >= 0) return rc;
     }
-    if (g_conv_w8 && g_conv_split == 1 && (int64_t)ceil_div(d->N, 128) * ceil_div(M, 128) >= g_conv_w8_min) {
+    if (knob.conv_w8 && knob.conv_split == 1 && (int64_t)ceil_div(d->N, 128) * ceil_div(M, 128) >= knob.conv_w8_min) {
       const int rc = launch_conv_split<SCfg128W8>(a, d->epi, stream);
       if (rc >= 0) return rc;
     }
-    if (g_conv_split == 3) return launch_conv_split<SCfgM64>(a, d->epi, stream);
-    if (g_conv_split == 4) return launch_conv_split<SCfg128>(a, d->epi, stream);
+    if (knob.conv_split == 3) return launch_conv_split<SCfgM64>(a, d->epi, stream);
+    if (knob.conv_split == 4) return launch_conv_split<SCfg128>(a, d->epi, stream);
     return narrow ? launch_conv_split<SCfgM64>(a, d->epi, stream) : launch_conv_split<SCfg128>(a, d->epi, stream);
   }
-  if (g_conv_tile == 3) return launch_conv<Cfg6464>(a, d->epi, stream);
-  if (g_conv_tile == 4) return launch_conv<Cfg6464K16>(a, d->epi, stream);
-  if (g_conv_tile == 5) return launch_conv<CfgM64K16>(a, d->epi, stream);
-  if (g_conv_tile == 2) return launch_conv<CfgM64>(a, d->epi, stream);
-  if (g_conv_tile == 1) return launch_conv<Cfg128>(a, d->epi, stream);
+  if (knob.conv_tile == 3) return launch_conv<Cfg6464>(a, d->epi, stream);
+  if (knob.conv_tile == 4) return launch_conv<Cfg6464K16>(a, d->epi, stream);
+  if (knob.conv_tile == 5) return launch_conv<CfgM64K16>(a, d->epi, stream);
+  if (knob.conv_tile == 2) return launch_conv<CfgM64>(a, d->epi, stream);
+  if (knob.conv_tile == 1) return launch_conv<Cfg128>(a, d->epi, stream);
   if ((int64_t)ceil_div(d->N, 128) * ceil_div(M, 128) < 512) return launch_conv<CfgM64>(a, d->epi, stream);
   return launch_conv<Cfg128>(a, d->epi, stream);
 }
@@ -2053,296 +1248,4 @@ extern "C" int fsraft_conv_workspace(float* ws, int64_t floats) {
   t_reg_ws = ws;
   t_reg_ws_floats = ws ? floats : 0;
   return FS_OK;
-}
-
-// Reads back the arithmetic-mode switches (key 3: forward / data-gradient convolutions, key 4: weight gradients); the
-// host side uses it to skip packing the exact-fp32 weight matrices while the split-bf16 kernels are the ones that run.
-extern "C" int fsraft_conv_last_route(int which) {
-  return which == 0 || which == 1 ? t_route[which] : -1;
-}
-
-extern "C" int fsraft_get_tuning(int key) {
-  if (key == 3) return g_conv_split;
-  if (key == 4) return g_wgrad_split;
-  return -1;
-}
-
-// fsraft.h: one switch for the arithmetic of every GEMM-shaped kernel of the library
-extern "C" int fsraft_set_build_split(int on);
-extern "C" int fsraft_set_gemm_split(int on);
-extern "C" int fsraft_set_arithmetic(int mode) {
-  if (mode != 0 && mode != 1) return FS_ERR_ARG;
-  g_conv_split = mode ? 1 : 0;
-  g_wgrad_split = mode ? 2 : 0;
-  fsraft_set_build_split(mode);
-  fsraft_set_gemm_split(mode);
-  return FS_OK;
-}
-extern "C" int fsraft_get_arithmetic(void) { return g_conv_split != 0 ? 1 : 0; }
-
-extern "C" int fsraft_set_tuning(int key, int value) {
-  if (key == 0) g_conv_tile = value;
-  else if (key == 1) g_wgrad_tile = value;
-  else if (key == 2) g_wgrad_blocks = value;
-  else if (key == 3) g_conv_split = value;
-  else if (key == 5) g_conv_buf = value;
-  else if (key == 8) g_wgrad_buf = value;
-  else if (key == 9) g_conv_n256 = value;
-  else if (key == 10) g_wgrad_multi = value;
-  else if (key == 11) g_wgrad_blocks_multi = value;
-  else if (key == 18) g_conv_n64 = value;
-  else if (key == 19) g_conv_n64_min_m = value;
-  else if (key == 20) g_conv_halo = value;
-  else if (key == 21) g_conv_halo_min_m = value;
-  else if (key == 22) g_wgrad_xcd = value;
-  else if (key == 26) g_conv_patch = value;
-  else if (key == 31) g_conv_patch_min_m = value;
-  else if (key == 32) g_conv_ksplit = value;
-  else if (key == 27) g_wgrad_patch = value;
-  else if (key == 28) g_conv_patch64 = value;
-  else if (key == 29) g_wgrad_patch1 = value;
-  else if (key == 16) g_wgrad_pack = value;
-  else if (key == 17) g_wgrad_blocks_pack = value;
-  else if (key == 12) g_conv_uniform = value;
-  else if (key == 13) g_conv_w8 = value;
-  else if (key == 14) g_conv_w8_min = value;
-  else if (key == 15) g_wgrad_w8 = value;
-  else if (key == 7) g_xcd_swizzle = value;
-  else if (key == 4) g_wgrad_split = value;
-  else return FS_ERR_ARG;
-  return FS_OK;
-}
-
-// dwpk[Cout][Ktot] += dY^T * im2col(X)   (same packed layout as the forward weights)
-extern "C" int fsraft_col_sum(const float* x, int ld, int64_t M, int C, float* out, float scale, hipStream_t s);
-
-namespace { int launch_wgrad_patch(WgradArgsM m, hipStream_t s); }
-
-extern "C" int fsraft_conv_wgrad(const float* dy, int ldy, int Cout, const float* const* src, const int* srcC,
-                                 const int* srcld, int nsrc, float* dwpk, float* dbias, int B, int H, int W, int KH,
-                                 int KW, hipStream_t stream) {
-  if (!dy || !src || !dwpk || nsrc < 1 || nsrc > 3 || ldy % 4 != 0) return FS_ERR_ARG;
-  t_route[1] = 0;
-  WgradArgs a{};
-  a.dy = dy; a.ldy = ldy; a.Cout = Cout;
-  const bool small_m = Cout <= 32;
-  const bool t64 = !small_m && g_wgrad_tile == 3;
-  const int bn = t64 ? 64 : 128, bm = small_m ? 32 : (t64 ? 64 : 128);
-  int xt128 = 0;
-  for (int s = 0; s < 3; ++s) {
-    a.src[s] = Src{s < nsrc ? src[s] : src[0], s < nsrc ? srcC[s] : 0, s < nsrc ? srcld[s] : 4};
-    if (s < nsrc) {
-      if (!src[s] || srcld[s] % 4 != 0) return FS_ERR_ARG;
-      xt128 += KH * KW * ceil_div(srcC[s], bn);
-    }
-  }
-  a.nsrc = nsrc; a.dwpk = dwpk; a.Ktot = conv_ktot(srcC, nsrc, KH * KW);
-  a.B = B; a.H = H; a.W = W; a.KH = KH; a.KW = KW;
-  const int64_t M = (int64_t)B * H * W;
-  // one segment of a 3x3 layer at encoder size: the resident-block kernel (wgrad_patch.inc) reads dY and X once instead of once
-  // per tap group
-  if (g_wgrad_patch && g_wgrad_patch1 && g_wgrad_split != 0 && KH == 3 && KW == 3 && Cout > 32 && M >= g_wgrad_patch1) {
-    WgradArgsM m{};
-    m.a = a; m.a.dbias = dbias;
-    m.nseg = 1;
-    m.dys[0] = dy;
-    for (int s = 0; s < nsrc; ++s) m.srcs[s][0] = src[s];
-    const int rc = launch_wgrad_patch(m, stream);
-    if (rc >= 0) return rc;
-  }
-  if (g_wgrad_pack && g_wgrad_split != 0 && g_wgrad_buf && nsrc == 1 && srcC[0] <= 96 && KH * KW > 1 &&
-      (int64_t)(32 * (WGRAD_PACK_WORDS - 2) + 2 * W + 2) * srcld[0] * 4 < 0x7fffffff) {
-    // few input channels: several taps per x tile, 64-row dY tiles (conv_wgrad_pack_kernel)
-    const int cpad = ceil_div(srcC[0], 32) * 32;
-    int tp = SWCfgPack::BN / cpad;
-    if (tp > WGRAD_PACK_SLOTS) tp = WGRAD_PACK_SLOTS;
-    const int xt = ceil_div(KH * KW, tp), yt = ceil_div(Cout, SWCfgPack::BM);
-    int64_t want = (g_wgrad_blocks_pack + (int64_t)xt * yt - 1) / ((int64_t)xt * yt);
-    if (want < 1) want = 1;
-    int64_t chunk = (M + want - 1) / want;
-    if (chunk < 256) chunk = 256;
-    if (chunk > 32 * (WGRAD_PACK_WORDS - 2)) chunk = 32 * (WGRAD_PACK_WORDS - 2);
-    chunk = (chunk + 31) / 32 * 32;
-    a.kchunk = (int)chunk;
-    a.dbias = dbias;
-    dim3 grid(xt, yt, (unsigned)((M + chunk - 1) / chunk));
-    if (g_wgrad_xcd == 2) {      // measured slower here (64 -> 64 at 8x220x512: 406 vs 377 us): three tap groups per dY tile only
-      a.xcd_xt = xt; a.xcd_yt = yt; a.xcd_groups = yt * (int)grid.z;
-      grid = dim3((unsigned)(ceil_div(a.xcd_groups, 8) * 8 * xt), 1, 1);
-    }
-    t_route[1] = 6;
-    hipLaunchKernelGGL((conv_wgrad_pack_kernel<SWCfgPack>), grid, dim3(SWCfgPack::NT), 0, stream, a);
-    return fs_launch_status();
-  }
-  const int ytiles = ceil_div(Cout, bm);
-  // aim for ~4 workgroups per CU; each split handles a multiple of 32 pixels, at least 256
-  int64_t want = (g_wgrad_blocks + (int64_t)xt128 * ytiles - 1) / ((int64_t)xt128 * ytiles);
-  if (want < 1) want = 1;
-  int64_t chunk = (M + want - 1) / want;
-  if (chunk < 256) chunk = 256;
-  if (chunk > 32 * (WGRAD_MASK_WORDS - 2)) chunk = 32 * (WGRAD_MASK_WORDS - 2);   // pixel-mask capacity of the buffer-addressed kernel
-  chunk = (chunk + 31) / 32 * 32;
-  a.kchunk = (int)chunk;
-  const int zs = (int)((M + chunk - 1) / chunk);
-  dim3 grid(xt128, ytiles, zs);
-  a.dbias = dbias;
-  const bool wbuf = g_wgrad_buf && chunk <= 32 * (WGRAD_MASK_WORDS - 2) && (int64_t)chunk * 4 * 2048 < 0x7fffffff;
-  if (!small_m && !t64 && g_wgrad_split == 1) {
-    t_route[1] = 4;
-    if (wbuf) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128>), grid, dim3(256), 0, stream, a);
-    return fs_launch_status();
-  }
-  if (!small_m && !t64 && g_wgrad_split == 2) {
-    t_route[1] = 5;
-    if (wbuf) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S>), grid, dim3(256), 0, stream, a);
-    return fs_launch_status();
-  }
-  // the exact-fp32 kernels do not fuse the bias gradient: separate column-sum pass
-  if (dbias) { const int rc = fsraft_col_sum(dy, ldy, M, Cout, dbias, 1.0f, stream); if (rc) return rc; }
-  t_route[1] = small_m ? 1 : t64 ? 2 : 3;
-  if (small_m) hipLaunchKernelGGL((conv_wgrad_kernel<WCfg32>), grid, dim3(256), 0, stream, a);
-  else if (t64) hipLaunchKernelGGL((conv_wgrad_kernel<WCfg6464>), grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv_wgrad_kernel<WCfg128>), grid, dim3(256), 0, stream, a);
-  return fs_launch_status();
-}
-
-// nseg (dY, X) pairs of identical shape in one launch; src[seg * nsrc + s].  Falls back to one launch per segment when
-// the buffer-addressed split kernel cannot take the shape.
-#include "wgrad_patch.inc"
-
-extern "C" int fsraft_conv_wgrad_multi(const float* const* dy, int nseg, int ldy, int Cout, const float* const* src,
-                                       const int* srcC, const int* srcld, int nsrc, float* dwpk, float* dbias, int B,
-                                       int H, int W, int KH, int KW, hipStream_t stream) {
-  if (!dy || !src || !dwpk || nseg < 1 || nsrc < 1 || nsrc > 3 || ldy % 4 != 0) return FS_ERR_ARG;
-  t_route[1] = 0;
-  const int64_t M = (int64_t)B * H * W;
-  const bool fast = g_wgrad_multi && nseg > 1 && Cout > 32 && g_wgrad_tile != 3 && g_wgrad_split == 2 && g_wgrad_buf;
-  for (int base = 0; base < nseg; base += WGRAD_MAX_SEG) {
-    const int n = nseg - base < WGRAD_MAX_SEG ? nseg - base : WGRAD_MAX_SEG;
-    if (!fast || n == 1) {
-      for (int i = 0; i < n; ++i) {
-        const int rc = fsraft_conv_wgrad(dy[base + i], ldy, Cout, src + (size_t)(base + i) * nsrc, srcC, srcld, nsrc, dwpk,
-                                         dbias, B, H, W, KH, KW, stream);
-        if (rc) return rc;
-      }
-      continue;
-    }
-    WgradArgsM m{};
-    WgradArgs& a = m.a;
-    a.dy = dy[base]; a.ldy = ldy; a.Cout = Cout;
-    int xt128 = 0;
-    for (int s = 0; s < 3; ++s) {
-      a.src[s] = Src{s < nsrc ? src[(size_t)base * nsrc + s] : src[(size_t)base * nsrc], s < nsrc ? srcC[s] : 0, s < nsrc ? srcld[s] : 4};
-      if (s < nsrc) {
-        if (srcld[s] % 4 != 0) return FS_ERR_ARG;
-        xt128 += KH * KW * ceil_div(srcC[s], 128);
-      }
-    }
-    for (int i = 0; i < n; ++i) {
-      if (!dy[base + i]) return FS_ERR_ARG;
-      m.dys[i] = dy[base + i];
-      for (int s = 0; s < nsrc; ++s) {
-        if (!src[(size_t)(base + i) * nsrc + s]) return FS_ERR_ARG;
-        m.srcs[s][i] = src[(size_t)(base + i) * nsrc + s];
-      }
-    }
-    a.nsrc = nsrc; a.dwpk = dwpk; a.Ktot = conv_ktot(srcC, nsrc, KH * KW);
-    a.B = B; a.H = H; a.W = W; a.KH = KH; a.KW = KW; a.dbias = dbias;
-    if (g_wgrad_patch && KH * KW > 1) {
-      m.nseg = n;
-      const int rc = launch_wgrad_patch(m, stream);
-      if (rc == 0) continue;
-      if (rc > 0) return rc;
-    }
-    const int ytiles = ceil_div(Cout, 128);
-    // ~g_wgrad_blocks workgroups in total, a whole number of pixel splits per segment
-    int64_t zs = (g_wgrad_blocks_multi + (int64_t)xt128 * ytiles * n - 1) / ((int64_t)xt128 * ytiles * n);
-    if (zs < 1) zs = 1;
-    int64_t chunk = (M + zs - 1) / zs;
-    if (chunk < 256) chunk = 256;
-    if (chunk > 32 * (WGRAD_MASK_WORDS - 2)) chunk = 32 * (WGRAD_MASK_WORDS - 2);
-    chunk = (chunk + 31) / 32 * 32;
-    if ((int64_t)chunk * 4 * 2048 >= 0x7fffffff) return FS_ERR_ARG;
-    a.kchunk = (int)chunk;
-    m.zs = (int)((M + chunk - 1) / chunk);
-    m.nseg = n;
-    dim3 grid(xt128, ytiles, m.zs * n);
-    if (g_wgrad_xcd == 3) {        // all tiles of one pixel split on one XCD (xcd_yt < 0 carries -x tiles)
-      m.a.xcd_xt = xt128 * ytiles; m.a.xcd_yt = -xt128; m.a.xcd_groups = m.zs * n;
-      grid = dim3((unsigned)(ceil_div(m.a.xcd_groups, 8) * 8 * xt128 * ytiles), 1, 1);
-    } else if (g_wgrad_xcd) {
-      m.a.xcd_xt = xt128; m.a.xcd_yt = ytiles; m.a.xcd_groups = ytiles * m.zs * n;
-      grid = dim3((unsigned)(ceil_div(m.a.xcd_groups, 8) * 8 * xt128), 1, 1);
-    }
-    t_route[1] = g_wgrad_w8 ? 9 : 8;
-    if (g_wgrad_w8) hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128W8, true, true>), grid, dim3(512), 0, stream, m);
-    else hipLaunchKernelGGL((conv_wgrad_split_kernel<SWCfg128S, true, true>), grid, dim3(256), 0, stream, m);
-    const int rc = fs_launch_status();
-    if (rc) return rc;
-  }
-  return FS_OK;
-}
-
-// mode 0: OIHW -> forward packed; mode 1: OIHW -> data-gradient packed (rows = Cin);
-// mode 2: packed (forward layout) -> OIHW, optionally accumulating.  srcC splits Cin for modes 0/2.
-extern "C" int fsraft_pack_conv_weights(const PackJob* jobs, int njobs, hipStream_t stream) {
-  if (njobs < 0 || (njobs && !jobs)) return FS_ERR_ARG;
-  for (int i = 0; i < njobs; ++i) {
-    const PackJob& j = jobs[i];
-    const int m = j.mode;
-    if (!(m == 0 || m == 1 || m == 2 || m == 3 || m == 10 || m == 11) || !j.wpk || j.npiece < 1 || j.npiece > 3) return FS_ERR_ARG;
-    for (int p = 0; p < j.npiece; ++p) if (!j.w[p] || j.rows[p] < 1) return FS_ERR_ARG;
-    if (m == 3) continue;
-    if (j.nsrc < 1 || j.nsrc > 3 || j.kh < 1 || j.kw < 1 || j.cin_full < 1) return FS_ERR_ARG;
-    if ((j.flags & 1) && m < 10) return FS_ERR_ARG;
-    if ((j.flags & 2) && (j.kh != 2 || j.kw != 2 || j.nsrc != 1 || j.srcC[0] != 4 * j.cin_full || j.srcOff[0] != 0)) return FS_ERR_ARG;
-    if (!(j.flags & 2)) for (int s = 0; s < j.nsrc; ++s) if (j.srcC[s] < 1 || j.srcOff[s] < 0 || j.srcOff[s] + j.srcC[s] > j.cin_full) return FS_ERR_ARG;
-  }
-  for (int i0 = 0; i0 < njobs; i0 += PACK_JOBS) {
-    PackJobs tab{};
-    const int n = njobs - i0 < PACK_JOBS ? njobs - i0 : PACK_JOBS;
-    int64_t most = 0;
-    for (int i = 0; i < n; ++i) {
-      tab.j[i] = jobs[i0 + i];
-      const PackJob& j = tab.j[i];
-      int64_t cout = 0, cin = 0;
-      for (int p = 0; p < j.npiece; ++p) cout += j.rows[p];
-      for (int s = 0; s < j.nsrc; ++s) cin += (j.srcC[s] + 31) / 32 * 32;
-      const int64_t tot = j.mode == 3 ? cout : ((cout + 31) / 32 * 32) * ((cin + 31) / 32 * 32) * j.kh * j.kw;
-      most = tot > most ? tot : most;
-    }
-    int blocks = (int)((most + 1023) / 1024);
-    blocks = blocks < 1 ? 1 : (blocks > 512 ? 512 : blocks);
-    hipLaunchKernelGGL(pack_jobs_kernel, dim3(blocks, n), dim3(256), 0, stream, tab);
-  }
-  return fs_launch_status();
-}
-
-extern "C" int fsraft_pack_conv_weight(float* w_oihw, float* wpk, int Cout, int Cin, int KH, int KW, const int* srcC,
-                                       int nsrc, int mode, int accumulate, hipStream_t stream) {
-  if (!w_oihw || !wpk || mode < 0 || (mode > 2 && mode != 10 && mode != 11)) return FS_ERR_ARG;
-  PackArgs a{};
-  a.split = mode >= 10;                      // modes 10 / 11: split-bf16 variants of modes 0 / 1
-  if (mode >= 10) mode -= 10;
-  if (a.split && mode > 1) return FS_ERR_ARG;
-  a.w = w_oihw; a.wpk = wpk; a.Cout = Cout; a.Cin = Cin; a.taps = KH * KW; a.mode = mode; a.accumulate = accumulate;
-  if (mode == 1) {
-    a.nsrc = 1; a.C[0] = Cout; a.C[1] = a.C[2] = 0;
-    a.Ktot = a.taps * (((Cout + 31) / 32) * 32);
-    a.rows = Cin;
-  } else {
-    if (!srcC || nsrc < 1 || nsrc > 3) return FS_ERR_ARG;
-    int tot = 0;
-    for (int s = 0; s < 3; ++s) { a.C[s] = s < nsrc ? srcC[s] : 0; tot += a.C[s]; }
-    if (tot != Cin) return FS_ERR_ARG;
-    a.nsrc = nsrc;
-    a.Ktot = conv_ktot(srcC, nsrc, a.taps);
-    a.rows = Cout;
-  }
-  const int64_t total = (int64_t)a.rows * a.Ktot;
-  int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(pack_weight_kernel, dim3(blocks), dim3(256), 0, stream, a);
-  return fs_launch_status();
 }

@@ -217,9 +217,7 @@ int launch_conv_patch_t(const PatchArgs& p, int epi, dim3 grid, hipStream_t s) {
       return fs_launch_status();
     }
   }
-  if (epi == EPI_PLAIN) hipLaunchKernelGGL((conv_patch_kernel<EPI_PLAIN, KH, KW, TH>), grid, dim3(TH * 64), 0, s, p);
-  else if (epi == EPI_ZR) hipLaunchKernelGGL((conv_patch_kernel<EPI_ZR, KH, KW, TH>), grid, dim3(TH * 64), 0, s, p);
-  else hipLaunchKernelGGL((conv_patch_kernel<EPI_Q, KH, KW, TH>), grid, dim3(TH * 64), 0, s, p);
+  with_epi(epi, [&](auto e) { hipLaunchKernelGGL((conv_patch_kernel<decltype(e)::value, KH, KW, TH>), grid, dim3(TH * 64), 0, s, p); });
   return fs_launch_status();
 }
 
@@ -254,8 +252,8 @@ int launch_conv_patch(const ConvArgs& a, int epi, hipStream_t s) {
   // (64-column tiles: 64 -> 64 at 8x220x512 runs 269 us on 256-pixel tiles, 257 us on 128-pixel tiles, 236 us on
   //  conv3x3_halo_kernel -- twelve MFMAs per wave between barriers are too few; 128 -> 64 at M = 28160: 32 us on 128-pixel
   //  tiles against 41 us on the 256x64 implicit GEMM.  So: small grids only, key 28 = 2 / 3 forces 128 / 256-pixel tiles.)
-  if (bn == 64 && wg8 >= 200 && g_conv_patch64 == 1) return -1;
-  if (wg8 >= 200 && !(bn == 64 && g_conv_patch64 == 2)) {
+  if (bn == 64 && wg8 >= 200 && knob.conv_patch64 == 1) return -1;
+  if (wg8 >= 200 && !(bn == 64 && knob.conv_patch64 == 2)) {
     dim3 grid(ceil_div(a.N, bn), p.tx * ceil_div(a.H, 8) * a.B);
     if (k33) return launch_conv_patch_t<3, 3, 8>(p, epi, grid, s);
     if (k15) return launch_conv_patch_t<1, 5, 8>(p, epi, grid, s);
@@ -266,7 +264,7 @@ int launch_conv_patch(const ConvArgs& a, int epi, hipStream_t s) {
   //  At one or two pairs per GPU (8832 / 13824 pixels) the 3x3 layers with two output tiles run 5-12 % faster here than on the
   //  138 / 216 workgroups of the implicit GEMM (3x3 256 -> 192: 65 -> 57.5 us, its data gradient 47 -> 43): adopted for those.
   const bool small_grid_33 = k33 && a.N > 128 && (int64_t)ceil_div(a.N, 128) * ceil_div(a.B * a.H * a.W, 128) > 120;
-  if (g_conv_patch != 2 && bn != 64 && !small_grid_33) return -1;
+  if (knob.conv_patch != 2 && bn != 64 && !small_grid_33) return -1;
   dim3 grid(ceil_div(a.N, bn), p.tx * ceil_div(a.H, 4) * a.B);
   if (k33) return launch_conv_patch_t<3, 3, 4>(p, epi, grid, s);
   if (k15) return launch_conv_patch_t<1, 5, 4>(p, epi, grid, s);

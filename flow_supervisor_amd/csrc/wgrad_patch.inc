@@ -1,4 +1,4 @@
-// Weight gradient of the 3x3 / 1x5 / 5x1 layers over RESIDENT PIXEL BLOCKS: included by conv_igemm.hip (WgradArgsM, loaders'
+// Weight gradient of the 3x3 / 1x5 / 5x1 layers over RESIDENT PIXEL BLOCKS: included by conv_wgrad.hip (WgradArgsM, loaders'
 // helpers, tr_frag, stage_convert_kmajor).
 //
 //     dW[co][tap][ci] += sum over the stashed iterations t and pixels p of dY_t[p][co] * X_t[p + shift(tap)][ci]
@@ -262,7 +262,7 @@ int launch_wgrad_patch(WgradArgsM m, hipStream_t s) {
   const WgradArgs& a = m.a;
   const bool k33 = a.KH == 3 && a.KW == 3, k15 = a.KH == 1 && a.KW == 5, k51 = a.KH == 5 && a.KW == 1;
   if (!(k33 || k15 || k51) || a.Cout <= 32) return -1;
-  if (!k33 && g_wgrad_patch < 2) return -1;                 // (key 27 = 2: the five-tap layers too)
+  if (!k33 && knob.wgrad_patch < 2) return -1;                 // (key 27 = 2: the five-tap layers too)
   WgradPatchArgs p;
   p.m = m;
   p.ty = ceil_div(a.H, WP_TH); p.tx = ceil_div(a.W, WP_TW);

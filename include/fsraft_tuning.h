@@ -17,17 +17,42 @@
 extern "C" {
 #endif
 
-/* key 0: conv tile (0 auto, 1 128x128, 2 64x128, 3 64x64); 1: wgrad tile (0 128x128, 3 64x64); 2 / 11 / 17: target
- * workgroup counts of the weight-gradient pixel splits; 3: arithmetic of the forward / data-gradient convolutions (0 exact
- * fp32, 1 bf16x3; 3 / 4 / 5 force a tile shape); 4: arithmetic of the weight gradients (0 exact, 2 bf16x3); 5 / 8:
- * buffer-addressed loaders; 7: XCD swizzle; 9 / 13 / 14 / 15 / 18 / 19: tile-shape thresholds; 12: uniform k-tile table;
- * 16: few-channel weight-gradient kernel; 20 / 21: resident-patch 3x3 encoder kernel and its minimum pixel count; 22:
- * XCD-aware weight-gradient order; 26: resident-patch forward / data-gradient kernel; 27: resident-block weight gradient
- * (0 off, 1 the 3x3 layers, 2 the five-tap layers too); 28: 64-column patch tiles; 29: single-segment resident-block
- * weight gradient, minimum pixel count; 31: minimum pixel count of the resident-patch forward / data-gradient kernel; 32: split-K slices of the small-M convolutions
- * (-1 auto, 0 off, >= 2 forced). */
+/* Keys of fsraft_set_tuning / fsraft_get_tuning: the knobs of the convolution family; any other number is no key. */
+enum fsraft_tuning_key {
+  FSRAFT_KEY_CONV_TILE = 0,            /* conv tile (0 auto, 1 128x128, 2 64x128, 3 64x64) */
+  FSRAFT_KEY_WGRAD_TILE = 1,           /* wgrad tile (0 128x128, 3 64x64) */
+  FSRAFT_KEY_WGRAD_BLOCKS = 2,         /* target workgroup count of the weight-gradient pixel split (11: of the multi-segment
+                                          launch, 17: of the few-channel kernel) */
+  FSRAFT_KEY_CONV_ARITH = 3,           /* arithmetic of the forward / data-gradient convolutions (0 exact fp32, 1 bf16x3;
+                                          3 / 4 / 5 force a tile shape) */
+  FSRAFT_KEY_WGRAD_ARITH = 4,          /* arithmetic of the weight gradients (0 exact, 2 bf16x3) */
+  FSRAFT_KEY_CONV_BUF = 5,             /* buffer-addressed loaders: forward / data gradient (8: weight gradient) */
+  FSRAFT_KEY_XCD_SWIZZLE = 7,          /* XCD swizzle */
+  FSRAFT_KEY_WGRAD_BUF = 8,
+  FSRAFT_KEY_CONV_N256 = 9,            /* tile-shape thresholds (9 / 13 / 14 / 15 / 18 / 19): 64x256 tiles */
+  FSRAFT_KEY_WGRAD_MULTI = 10,         /* one weight-gradient launch per layer over all iterations of a step */
+  FSRAFT_KEY_WGRAD_BLOCKS_MULTI = 11,
+  FSRAFT_KEY_CONV_UNIFORM = 12,        /* uniform k-tile table */
+  FSRAFT_KEY_CONV_W8 = 13,             /* eight- / sixteen-wave tiles for wide layers (14: minimum workgroup count) */
+  FSRAFT_KEY_CONV_W8_MIN = 14,
+  FSRAFT_KEY_WGRAD_W8 = 15,            /* eight-wave workgroups in the multi-segment weight gradient */
+  FSRAFT_KEY_WGRAD_PACK = 16,          /* few-channel weight-gradient kernel */
+  FSRAFT_KEY_WGRAD_BLOCKS_PACK = 17,
+  FSRAFT_KEY_CONV_N64 = 18,            /* 256x64 tiles for N <= 64 (19: minimum pixel count) */
+  FSRAFT_KEY_CONV_N64_MIN_M = 19,
+  FSRAFT_KEY_CONV_HALO = 20,           /* 20 / 21: resident-patch 3x3 encoder kernel and its minimum pixel count */
+  FSRAFT_KEY_CONV_HALO_MIN_M = 21,
+  FSRAFT_KEY_WGRAD_XCD = 22,           /* XCD-aware weight-gradient order */
+  FSRAFT_KEY_CONV_PATCH = 26,          /* resident-patch forward / data-gradient kernel */
+  FSRAFT_KEY_WGRAD_PATCH = 27,         /* resident-block weight gradient (0 off, 1 the 3x3 layers, 2 the five-tap layers too) */
+  FSRAFT_KEY_CONV_PATCH64 = 28,        /* 64-column patch tiles */
+  FSRAFT_KEY_WGRAD_PATCH1 = 29,        /* single-segment resident-block weight gradient, minimum pixel count */
+  FSRAFT_KEY_CONV_PATCH_MIN_M = 31,    /* minimum pixel count of the resident-patch forward / data-gradient kernel */
+  FSRAFT_KEY_CONV_KSPLIT = 32          /* split-K slices of the small-M convolutions (-1 auto, 0 off, >= 2 forced) */
+};
+/* set: FSRAFT_OK, or FSRAFT_ERR_ARG for a key that is not in the enum.  get: the knob's value, INT_MIN for such a key. */
 int fsraft_set_tuning(int key, int value);
-int fsraft_get_tuning(int key);   /* keys 3 / 4 */
+int fsraft_get_tuning(int key);
 /* Route attestation: the kernel the CALLING THREAD's last convolution ran (0 none / rejected call, -1 bad `which`).
  * which 0, fsraft_conv_forward (forward and data-gradient calls):
  *   exact-fp32 implicit GEMM tiles  1 Cfg32 (N <= 32, either mode), 2 Cfg64, 3 64x128, 4 128x128, 5 64x64 (key 0 = 3),

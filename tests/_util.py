@@ -6,6 +6,11 @@ import torch
 
 G = os.path.join(os.path.dirname(__file__), "golden")
 
+# fsraft_get_tuning(key) of a freshly loaded library, as the knobs stood before they became one struct (csrc/conv_common.hpp
+# ConvKnobs).  Keys 3 / 4 are the arithmetic mode (fsraft_set_arithmetic: 1 / 2 in the default mode, 0 / 0 in the exact one).
+TUNING_DEFAULTS = {0: 0, 1: 0, 2: 512, 5: 1, 7: 0, 8: 1, 9: 0, 10: 1, 11: 2048, 12: 1, 13: 1, 14: 64, 15: 0, 16: 1, 17: 1024, 18: 1,
+                   19: 65536, 20: 1, 21: 65536, 22: 1, 26: 1, 27: 1, 28: 1, 29: 8192, 31: 8192, 32: -1}
+
 
 def load(name):
     return dict(np.load(os.path.join(G, name + ".npz")))

@@ -29,6 +29,41 @@ def test_boundary_header_carries_no_tuning_knobs():
             assert lib.fsraft_set_tuning(key, 0) == 1
 
 
+def tuning_keys():
+    """The keys of fsraft_set_tuning / fsraft_get_tuning: enum fsraft_tuning_key of fsraft_tuning.h, name -> number."""
+    txt = open(os.path.join(ROOT, "include", "fsraft_tuning.h")).read()
+    body = txt[txt.index("enum fsraft_tuning_key {"):]
+    body = re.sub(r"/\*.*?\*/", "", body[:body.index("};")], flags=re.S)
+    return {name: int(num) for name, num in re.findall(r"(FSRAFT_KEY_\w+)\s*=\s*(-?\d+)", body)}
+
+
+def test_get_tuning_answers_for_every_key():
+    """fsraft_get_tuning reads every knob fsraft_set_tuning writes: the defaults, set followed by get, and the refusal of
+    numbers that are no keys (set: FSRAFT_ERR_ARG, get: INT_MIN; -1 would be the default of key 32).  Host code only."""
+    from _util import TUNING_DEFAULTS
+    from flow_supervisor_amd import _lib
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    lib.fsraft_set_tuning.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.fsraft_get_tuning.argtypes = [ctypes.c_int]
+    keys = sorted(tuning_keys().values())
+    assert len(keys) == len(tuning_keys()) and keys == sorted(list(TUNING_DEFAULTS) + [3, 4])
+    arith = {3: (0, 1), 4: (0, 2)}                       # the arithmetic mode the process runs in
+    for k in keys:
+        got = lib.fsraft_get_tuning(k)
+        assert got in arith[k] if k in arith else got == TUNING_DEFAULTS[k], (k, got)
+    for k in keys:
+        before = lib.fsraft_get_tuning(k)
+        try:
+            for v in (before + 7, -3, before):
+                assert lib.fsraft_set_tuning(k, v) == 0
+                assert lib.fsraft_get_tuning(k) == v, (k, v)
+        finally:
+            lib.fsraft_set_tuning(k, before)
+    for k in (6, 23, 24, 25, 30, 33, -1):
+        assert lib.fsraft_set_tuning(k, 0) == 1, k
+        assert lib.fsraft_get_tuning(k) == -2 ** 31, k
+
+
 def test_library_exports_every_declared_symbol():
     from flow_supervisor_amd import _lib
     names = header_symbols()

@@ -17,7 +17,7 @@ import pytest
 import torch
 
 import _convref as R
-from _util import _log_margin
+from _util import TUNING_DEFAULTS, _log_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -47,16 +47,15 @@ def precision(request):
 
 
 class tuning:
-    """fsraft_set_tuning(key, value) for the duration of a case; the defaults of conv_igemm.hip are put back in `finally`
-    (keys 3 / 4: the arithmetic mode the case started in)."""
-    DEFAULT = {0: 0, 1: 0, 5: 1, 9: 0, 15: 0, 27: 1, 28: 1, 32: -1}
+    """fsraft_set_tuning(key, value) for the duration of a case; what fsraft_get_tuning read before is put back in `finally`
+    (the defaults of csrc/conv_common.hpp; keys 3 / 4: the arithmetic mode the case started in)."""
 
     def __init__(self, knobs):
         self.knobs = dict(knobs or {})
 
     def __enter__(self):
         lib = _lib().load()
-        self.saved = {k: (lib.fsraft_get_tuning(k) if k in (3, 4) else self.DEFAULT[k]) for k in self.knobs}
+        self.saved = {k: lib.fsraft_get_tuning(k) for k in self.knobs}
         for k, v in self.knobs.items():
             assert lib.fsraft_set_tuning(k, v) == 0
 
@@ -1203,3 +1202,11 @@ def test_production_call(i, precision, request):
         r, *res, ok_bias = run_wgrad(case)
         _judge(kind, _case_id(request), r, route, precision, res)
         assert ok_bias, "bias gradient"
+
+
+def test_every_knob_is_back_at_its_default():
+    """Last in the file: whatever the cases above switched (`tuning`, the `precision` fixture) was put back -- every key reads
+    its default again, so the tests that run after this file see the library as it loads."""
+    lib = _lib().load()
+    got = {k: lib.fsraft_get_tuning(k) for k in list(TUNING_DEFAULTS) + [3, 4]}
+    assert got == {**TUNING_DEFAULTS, 3: 1, 4: 2}

@@ -8,7 +8,7 @@ resolves to the HIP runtime torch already loaded (one runtime per process).
 import ctypes
 import functools
 import os
-from ctypes import POINTER, Structure, c_float, c_int, c_int64, c_void_p
+from ctypes import POINTER, Structure, c_double, c_float, c_int, c_int64, c_void_p
 
 import torch
 
@@ -86,7 +86,7 @@ SIGNATURES = {
     "fsraft_set_arithmetic": [c_int],
     "fsraft_get_arithmetic": [],
     "fsraft_set_tuning": [c_int, c_int],
-    "fsraft_adamw_flat": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_float, c_float, c_float,
+    "fsraft_adamw_flat": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_double, c_double, c_float,
                           c_float, c_void_p, c_void_p, _S],
     "fsraft_stream_capture_id": [_S, c_void_p],
     "fsraft_stem_slots": [],

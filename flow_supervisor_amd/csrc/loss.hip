@@ -9,6 +9,13 @@
 namespace {
 
 constexpr int LOSS_MAX_PRED = 32;
+constexpr int LOSS_MAX_WG = 2048;
+// The six sums of a launch are formed in two stages: every workgroup leaves its partial sums here, and the one that arrives
+// last adds them up in float64, in workgroup order, and adds the result to `out` once.  (2048 fp32 atomicAdds onto one cell,
+// each a 1/2048 share of it, lost up to 11 units of 2^-24 of the loss at 525312 pixels -- in the order the workgroups happened to
+// retire, so not the same twice.)  One launch at a time per device: launches on one stream, or ordered otherwise.
+__device__ float g_loss_part[LOSS_MAX_WG * 6];
+__device__ unsigned int g_loss_ticket;   // workgroups of the running launch that have left their sums; the last one resets it
 struct LossArgs {
   const float* pred[LOSS_MAX_PRED];
   float* dpred[LOSS_MAX_PRED];          // nullptr: no gradient for that prediction
@@ -29,6 +36,8 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 __global__ __launch_bounds__(256) void sequence_loss_kernel(LossArgs a) {
   __shared__ float red[4][6];
+  __shared__ double fin[4][6];
+  __shared__ bool last;
   const auto* karg = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
   typedef const float* cfptr;
   typedef float* fptr;
@@ -66,12 +75,37 @@ __global__ __launch_bounds__(256) void sequence_loss_kernel(LossArgs a) {
     for (int k = 0; k < 6; ++k) red[threadIdx.x >> 6][k] = acc[k];
   }
   __syncthreads();
-  if (threadIdx.x < 6) atomicAdd(a.out + threadIdx.x, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+  if (threadIdx.x < 6) {
+    g_loss_part[blockIdx.x * 6 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    __threadfence();
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) last = atomicAdd(&g_loss_ticket, 1u) == gridDim.x - 1;
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (unsigned int b = threadIdx.x; b < gridDim.x; b += 256) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s[k] += (double)__hip_atomic_load(&g_loss_part[b * 6 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_xor(s[k], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) fin[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) atomicAdd(a.out + threadIdx.x, (float)((fin[0][threadIdx.x] + fin[1][threadIdx.x]) + (fin[2][threadIdx.x] + fin[3][threadIdx.x])));
+  if (threadIdx.x == 0) g_loss_ticket = 0;
 }
 
 }  // namespace
 
-// out[6] must be zeroed by the caller.  dpred[i] may be NULL.  preds / gt are [B,2,H,W] contiguous, valid [B,H,W].
+// out[6] must be zeroed by the caller (or hold sums to add to).  dpred[i] may be NULL.  Launches on one device must not overlap.  preds / gt are [B,2,H,W] contiguous, valid [B,H,W].
 extern "C" int fsraft_sequence_loss(const float* const* pred, float* const* dpred, const float* weights, int n, int metric_idx,
                                     const float* gt, const float* valid, float max_flow, float eps, int B, int H, int W,
                                     float* out, hipStream_t s) {
@@ -85,7 +119,7 @@ extern "C" int fsraft_sequence_loss(const float* const* pred, float* const* dpre
   a.B = B; a.HW = H * W; a.out = out;
   const int64_t npix = (int64_t)B * H * W;
   int blocks = (int)((npix + 255) / 256);
-  if (blocks > 2048) blocks = 2048;
+  if (blocks > LOSS_MAX_WG) blocks = LOSS_MAX_WG;
   hipLaunchKernelGGL(sequence_loss_kernel, dim3(blocks), dim3(256), 0, s, a);
   return fs_launch_status();
 }

@@ -8,29 +8,34 @@ namespace {
 
 struct AdamState { float coef, step_size, inv_sqrt_bias2, decay; };
 
-// step (fp32 count, on the device: the captured hipGraph replays it) += 1; the scalars of this step
+// step (fp32 count, on the device: the captured hipGraph replays it) += 1; the scalars of this step.  The two bias corrections
+// are formed in double from the unrounded betas, as torch forms them: 1 - powf(fp32(0.999), 1) is 0.0009999871, 1.3e-5 off 0.001
+// and 108 units of 2^-24 in inv_sqrt_bias2.  One thread: the double pow costs nothing.
 __global__ void adamw_prepare_kernel(float* __restrict__ step, const float* __restrict__ norm, float max_norm,
-                                     const float* __restrict__ lr, float beta1, float beta2, float wd, AdamState* __restrict__ st) {
+                                     const float* __restrict__ lr, double beta1, double beta2, float wd, AdamState* __restrict__ st) {
   const float t = step[0] + 1.f;
   step[0] = t;
-  const float bias1 = 1.f - powf(beta1, t), bias2 = 1.f - powf(beta2, t), l = lr[0];
+  const double bias1 = 1.0 - pow(beta1, (double)t), bias2 = 1.0 - pow(beta2, (double)t);
+  const float l = lr[0];
   float coef = 1.f;
   if (norm) {                                    // torch.nn.utils.clip_grad_norm_: max_norm / (total + 1e-6), clamped to 1
     coef = max_norm / (norm[0] + 1e-6f);
     coef = coef < 1.f ? coef : 1.f;
   }
   st->coef = coef;
-  st->step_size = l / bias1;
-  st->inv_sqrt_bias2 = 1.f / sqrtf(bias2);
+  st->step_size = (float)((double)l / bias1);
+  st->inv_sqrt_bias2 = (float)(1.0 / sqrt(bias2));
   st->decay = 1.f - l * wd;
 }
 
 // torch.optim.AdamW (amsgrad = False, maximize = False), operation for operation as its fused kernel:
 //   p *= 1 - lr wd;  m += (1 - b1)(g - m);  v = b2 v + (1 - b2) g^2;  p -= (lr / bias1) m / (sqrt(v) / sqrt(bias2) + eps)
-// with g the clipped gradient, which is also written back (clip_grad_norm_ scales the gradients in place).
+// with g the clipped gradient, which is also written back (clip_grad_norm_ scales the gradients in place).  omb1 / omb2 are
+// 1 - beta rounded once from double (the host forms them): 1.f - fp32(0.999) is 1.3e-5 off 0.001, 216 units of 2^-24 in v.
 __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, int64_t n4, int64_t n, const AdamState* __restrict__ st,
-                                                         float beta1, float beta2, float eps, const unsigned char* __restrict__ skip) {
+                                                         float omb1, float beta2, float omb2, float eps,
+                                                         const unsigned char* __restrict__ skip) {
   const AdamState s = *st;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
     // skip[j] != 0: elements [64 j, 64 j + 64) belong to a tensor that received no gradient this step; torch's AdamW leaves
@@ -43,8 +48,8 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
       const float gg = gv[k] * s.coef;
       gv[k] = gg;
       float pp = pv[k] * s.decay;
-      mv[k] = mv[k] + (1.f - beta1) * (gg - mv[k]);
-      vv[k] = beta2 * vv[k] + (1.f - beta2) * gg * gg;
+      mv[k] = mv[k] + omb1 * (gg - mv[k]);
+      vv[k] = beta2 * vv[k] + omb2 * gg * gg;
       pp -= s.step_size * mv[k] / (sqrtf(vv[k]) * s.inv_sqrt_bias2 + eps);
       pv[k] = pp;
     }
@@ -56,8 +61,8 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
     const float gg = g[i] * s.coef;
     g[i] = gg;
     float pp = p[i] * s.decay;
-    m[i] = m[i] + (1.f - beta1) * (gg - m[i]);
-    v[i] = beta2 * v[i] + (1.f - beta2) * gg * gg;
+    m[i] = m[i] + omb1 * (gg - m[i]);
+    v[i] = beta2 * v[i] + omb2 * gg * gg;
     pp -= s.step_size * m[i] / (sqrtf(v[i]) * s.inv_sqrt_bias2 + eps);
     p[i] = pp;
   }
@@ -67,9 +72,10 @@ __global__ __launch_bounds__(256) void adamw_flat_kernel(float* __restrict__ p, 
 
 // One AdamW step on flat fp32 buffers of n elements (16-byte aligned).  step: device fp32 step count (incremented here);
 // norm: device scalar, the gradient's 2-norm (null: no clipping); lr: device scalar; state: 4 floats of scratch;
+// beta1 / beta2: double, as the caller's optimizer holds them (the bias corrections and 1 - beta are formed from them unrounded);
 // skip64 (nullable): ceil(n / 64) bytes, non-zero = leave that 64-element block alone (a parameter without a gradient).
 extern "C" int fsraft_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, float* step, const float* norm, float max_norm,
-                                 const float* lr, float beta1, float beta2, float eps, float weight_decay, float* state,
+                                 const float* lr, double beta1, double beta2, float eps, float weight_decay, float* state,
                                  const unsigned char* skip64, hipStream_t stream) {
   if (!p || !g || !m || !v || !step || !lr || !state || n < 1) return FS_ERR_ARG;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return FS_ERR_ARG;
@@ -82,7 +88,7 @@ extern "C" int fsraft_adamw_flat(float* p, float* g, float* m, float* v, int64_t
   if (blocks > 4096) blocks = 4096;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_flat_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p, g, m, v, n4, n,
-                     reinterpret_cast<const AdamState*>(state), beta1, beta2, eps, skip64);
+                     reinterpret_cast<const AdamState*>(state), (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), eps, skip64);
   return fs_launch_status();
 }
 

@@ -290,9 +290,11 @@ __global__ __launch_bounds__(256) void upflow8_bwd_kernel(const float* __restric
   const int64_t nc = e / ((int64_t)W * H);
   const float sy = H8 > 1 ? (float)(H - 1) / (float)(H8 - 1) : 0.f;
   const float sx = W8 > 1 ? (float)(W - 1) / (float)(W8 - 1) : 0.f;
-  // fine rows Y with floor(sy*Y) in {y-1, y}: conservative range then exact test
-  const int Ylo = max(0, (int)floorf((y - 1) / fmaxf(sy, 1e-12f)) - 1), Yhi = min(H8 - 1, (int)ceilf((y + 1) / fmaxf(sy, 1e-12f)) + 1);
-  const int Xlo = max(0, (int)floorf((x - 1) / fmaxf(sx, 1e-12f)) - 1), Xhi = min(W8 - 1, (int)ceilf((x + 1) / fmaxf(sx, 1e-12f)) + 1);
+  // fine rows Y with floor(sy*Y) in {y-1, y}: conservative range then exact test.  H == 1 (W == 1): the scale is 0, every fine
+  // row (column) sits on source row (column) 0, so the range is the whole axis -- no division
+  int Ylo = 0, Yhi = H8 - 1, Xlo = 0, Xhi = W8 - 1;
+  if (sy > 0.f) { Ylo = max(0, (int)floorf((y - 1) / sy) - 1); Yhi = min(H8 - 1, (int)ceilf((y + 1) / sy) + 1); }
+  if (sx > 0.f) { Xlo = max(0, (int)floorf((x - 1) / sx) - 1); Xhi = min(W8 - 1, (int)ceilf((x + 1) / sx) + 1); }
   const float* g = dup + nc * H8 * W8;
   float s = 0.f;
   for (int Y = Ylo; Y <= Yhi; ++Y) {

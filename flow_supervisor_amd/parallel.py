@@ -329,7 +329,7 @@ class FlatAdamW(torch.optim.Optimizer):
         b1, b2 = self.betas
         L.check(L.load().fsraft_adamw_flat(L.ptr(self.p), L.ptr(g), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), g.numel(),
                                            L.ptr(self.step_count), L.ptr(norm), ctypes.c_float(float(clip) if clip is not None else 0.0),
-                                           L.ptr(self.lr), ctypes.c_float(b1), ctypes.c_float(b2),
+                                           L.ptr(self.lr), ctypes.c_double(b1), ctypes.c_double(b2),
                                            ctypes.c_float(self.eps), ctypes.c_float(self.weight_decay), L.ptr(self._state),
                                            L.ptr(skip), L.stream()),
                 "adamw_flat")

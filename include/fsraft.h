@@ -376,7 +376,8 @@ int fsraft_affine_relu_bwd(const float* g, const float* x, const float* scale, c
  * loss = sum_i weights[i] * mean(mask * sqrt((pred_i - gt)^2 + eps^2)), mask = valid >= 0.5 && |gt| < max_flow, over n
  * predictions [B,2,H,W] in one pass; dpred[i] (nullable) receives d loss / d pred_i; out[0] = loss, out[1..5] = EPE sum,
  * counts < 1 / 3 / 5 px and valid (> 0.5) count of prediction metric_idx.  gt / valid may be NULL (zero flow / all valid).
- * out[6] must be zero on entry. */
+ * out[6] must be zero on entry (or hold sums: the launch adds to it, once, the float64 total of its workgroups' partial sums,
+ * so a result does not depend on the order the workgroups retire in).  Launches on one device must not overlap: one stream. */
 int fsraft_sequence_loss(const float* const* pred, float* const* dpred, const float* weights, int n, int metric_idx,
                          const float* gt, const float* valid, float max_flow, float eps, int B, int H, int W, float* out,
                          hipStream_t stream);
@@ -456,10 +457,11 @@ int fsraft_stem7x7s2_wgrad(const float* x, const float* dy, float* dw, float* sc
  * lr, weight_decay, eps)` (pytorch/train.py:137, 280-282) on FLAT fp32 buffers: parameters p, gradients g (scaled in place
  * like clip_grad_norm_ does), first / second moments m, v, n elements each.  step: device fp32 step count, incremented here;
  * norm: device scalar holding the gradients' 2-norm (null: no clipping); lr: device scalar; state: 4 floats of scratch;
+ * beta1 / beta2: double, unrounded (torch forms the bias corrections 1 - beta^step and 1 - beta in double);
  * skip64 (nullable): ceil(n / 64) bytes, non-zero = the 64-element block belongs to a parameter that received no gradient
  * this step and is left untouched with its moments (torch's AdamW skips `p.grad is None`). */
 int fsraft_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, float* step, const float* norm, float max_norm,
-                      const float* lr, float beta1, float beta2, float eps, float weight_decay, float* state,
+                      const float* lr, double beta1, double beta2, float eps, float weight_decay, float* state,
                       const unsigned char* skip64, hipStream_t stream);
 /* Host helper (no device work): *id = 0 when `stream` is not being captured into a hipGraph, else the capture's id.  The
  * binding keys per-capture scratch (zero-filled accumulation targets) on it. */

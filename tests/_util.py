@@ -93,3 +93,42 @@ def rel_check(value, ref, rtol, what):
     err, lim = abs(float(value) - float(ref)), rtol * abs(float(ref))
     _log_margin(what, err, lim, f"{rtol:g} * |ref| {abs(float(ref)):.6g}")
     assert err <= lim, f"{what}: {float(value)!r} vs reference {float(ref)!r} (rel {err / max(abs(float(ref)), 1e-30):.2e} > {rtol:g})"
+
+
+PATTERN = 0x7FC0FFEE            # guard rows and unwritten outputs: a NaN, so a read of one shows as well
+GUARD = 64                      # floats per guard row (256 bytes: the payload keeps the allocation's alignment)
+
+
+class Buf:
+    """A flat fp32 device buffer of n floats between two guard rows.  src: a CPU tensor to hold (an input); otherwise the payload
+    is PATTERN (an output) or zero.  offset: floats the payload is moved off its 16-byte alignment by."""
+
+    def __init__(self, src=None, n=None, zero=False, offset=0):
+        self.n = src.numel() if src is not None else n
+        self.off = GUARD + offset
+        self.whole = torch.empty(self.n + 2 * GUARD + offset, device="cuda", dtype=torch.float32)
+        self.whole.view(torch.int32).fill_(PATTERN)
+        self.mid = self.whole[self.off:self.off + self.n]
+        assert self.mid.data_ptr() % 16 == 4 * (offset % 4)
+        if src is not None:
+            self.mid.copy_(src.reshape(-1).float())
+        elif zero:
+            self.mid.zero_()
+
+    def cpu(self):
+        return self.mid.cpu()
+
+    def intact(self):
+        w = self.whole.view(torch.int32)
+        assert bool((w[:self.off] == PATTERN).all()) and bool((w[self.off + self.n:] == PATTERN).all()), "a guard row was written"
+
+    def written(self, upto=None):
+        """Guards intact and no pattern left in the payload (in its first `upto` floats; the rest still all pattern)."""
+        self.intact()
+        m = self.mid.view(torch.int32)
+        upto = self.n if upto is None else upto
+        assert not bool((m[:upto] == PATTERN).any()), "an output element was not written"
+        assert bool((m[upto:] == PATTERN).all()), "an output that was not asked for was written"
+
+    def untouched(self):
+        assert bool((self.whole.view(torch.int32) == PATTERN).all()), "a refused call wrote an output"

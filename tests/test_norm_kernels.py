@@ -46,12 +46,10 @@ import pytest
 import torch
 
 import _normref as R
-from _util import _log_margin
+from _util import Buf, _log_margin
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-PATTERN = 0x7FC0FFEE            # guard rows and unwritten outputs: a NaN, so a read of one shows as well
-G = 64                          # floats per guard row (256 bytes: the payload keeps the allocation's alignment)
 FS_ERR_ARG = 1
 VARIANTS = tuple(itertools.product((0, 1), (False, True)))          # (relu, with residual)
 
@@ -70,41 +68,6 @@ def L():
     from flow_supervisor_amd import _lib
     _lib.load()
     return _lib
-
-
-class Buf:
-    """A flat fp32 device buffer of n floats between two guard rows.  src: a CPU tensor to hold (an input); otherwise the payload
-    is PATTERN (an output) or zero.  offset: floats the payload is moved off its 16-byte alignment by."""
-
-    def __init__(self, src=None, n=None, zero=False, offset=0):
-        self.n = src.numel() if src is not None else n
-        self.off = G + offset
-        self.whole = torch.empty(self.n + 2 * G + offset, device=DEV, dtype=torch.float32)
-        self.whole.view(torch.int32).fill_(PATTERN)
-        self.mid = self.whole[self.off:self.off + self.n]
-        assert self.mid.data_ptr() % 16 == 4 * (offset % 4)
-        if src is not None:
-            self.mid.copy_(src.reshape(-1).float())
-        elif zero:
-            self.mid.zero_()
-
-    def cpu(self):
-        return self.mid.cpu()
-
-    def intact(self):
-        w = self.whole.view(torch.int32)
-        assert bool((w[:self.off] == PATTERN).all()) and bool((w[self.off + self.n:] == PATTERN).all()), "a guard row was written"
-
-    def written(self, upto=None):
-        """Guards intact and no pattern left in the payload (in its first `upto` floats; the rest still all pattern)."""
-        self.intact()
-        m = self.mid.view(torch.int32)
-        upto = self.n if upto is None else upto
-        assert not bool((m[:upto] == PATTERN).any()), "an output element was not written"
-        assert bool((m[upto:] == PATTERN).all()), "an output that was not asked for was written"
-
-    def untouched(self):
-        assert bool((self.whole.view(torch.int32) == PATTERN).all()), "a refused call wrote an output"
 
 
 def _p(L, b, lo=0):

@@ -145,6 +145,10 @@ SIGNATURES = {
     "fsraft_corr_build_tiled": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
     "fsraft_corr_build_rec": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
     "fsraft_corr_lookup_tiled_fwd": [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
+    "fsraft_corr_lookup_tiled_dcoords": [c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                         c_int, c_int, c_int, c_int, c_int, _S],
+    "fsraft_corr_lookup_dcoords": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64,
+                                   c_int, c_int, c_int, c_int, _S],
     "fsraft_corr_dvol_build": [_PP, _PP, POINTER(c_int64), c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
                                c_int64, c_void_p, c_void_p, _S],
     "fsraft_set_alt_tile": [c_int],

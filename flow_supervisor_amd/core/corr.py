@@ -13,8 +13,15 @@ is written ONCE (fsraft_corr_dvol_build: every query row accumulated in LDS over
 lookups of the step, no zero fill, no read-modify-write) and two GEMMs that contract over
 whole rows produce dF1 / dF2; the pooling chain's backward runs on the 7 MB feature
 gradient, not on the 1 GB volume gradient.  A 1-element "anchor" tensor threads the
-dependency through the autograd graph.  Coordinates get no gradient: every caller
-detaches them first (raft.py:123).
+dependency through the autograd graph.
+
+Coordinates: ``CorrBlock(...)(coords)`` is differentiable in the coordinates as the
+reference's grid_sample is.  The RAFT / L2L / GMA loops detach them (raft.py:123) and run
+exactly the nodes and launches they always did; a caller whose ``coords`` require grad
+gets ``coords.grad`` from fsraft_corr_lookup_tiled_dcoords (csrc/corr_dcoords.hip), one
+gather per lookup, also from a block whose feature maps take no gradient.  First
+derivatives only.  ``AlternateCorrBlock`` gives the coordinates no gradient: the
+reference's extension returns an all-zero coords_grad there (correlation_kernel.cu:307).
 """
 import math
 
@@ -93,24 +100,38 @@ class _BuildFn(torch.autograd.Function):
 
 
 class _LookupFn(torch.autograd.Function):
+    """One lookup.  anchor: the build node's 1-element output (None for a block whose feature maps take no gradient: the node
+    then exists for the coordinate gradient alone).  The volume gradient is not formed here -- backward hands (coords, dOut) to
+    the block's state -- but the coordinate gradient is: when `coords` requires grad, backward returns
+    ops.corr_lookup_tiled_dcoords(...), a gather over the same windows the forward read.  Only in that case the node keeps the
+    volume tensor and its layout (not the block: see the reference-cycle note in _AltBuildFn), so the volume then lives until
+    this node's backward has run or the graph is freed; with detached coordinates nothing but the coordinates is kept."""
+
     @staticmethod
     def forward(ctx, anchor, coords, block, channels_last, is_flow, out_buf=None):
         out = ops.corr_lookup_tiled_fwd(block._vol, block._lay, coords, block.radius, is_flow, out=out_buf)
-        ctx.state = block._state
+        ctx.state = block._state if anchor is not None else None
         ctx.cl, ctx.is_flow = channels_last, is_flow
+        if ctx.needs_input_grad[1]:
+            ctx.vol, ctx.lay, ctx.radius = block._vol, block._lay, block.radius
         ctx.save_for_backward(coords)
         return out if channels_last else ops.nhwc_to_nchw(out)
 
     @staticmethod
     def backward(ctx, dout):
-        (coords,) = ctx.saved_tensors
+        coords = ctx.saved_tensors[0].detach()
         dout = dout.contiguous() if ctx.cl else ops.nchw_to_nhwc(dout)
-        if ctx.is_flow != ctx.state.is_flow:       # (a block looked up both ways: keep one convention in the stash)
-            B, _, H, W = coords.shape
-            g = coords_grid(B, H, W, device=coords.device)
-            coords = coords - g if ctx.state.is_flow else coords + g
-        ctx.state.stash.append((coords, dout))
-        return None, None, None, None, None, None   # (no gradient tensor for the anchor: the build node still runs after every lookup)
+        dcoords = None
+        if ctx.needs_input_grad[1]:
+            dcoords = ops.corr_lookup_tiled_dcoords(ctx.vol, ctx.lay, coords, dout, ctx.radius, ctx.is_flow)
+            ctx.vol = None
+        if ctx.state is not None:
+            if ctx.is_flow != ctx.state.is_flow:       # (a block looked up both ways: keep one convention in the stash)
+                B, _, H, W = coords.shape
+                g = coords_grid(B, H, W, device=coords.device)
+                coords = coords - g if ctx.state.is_flow else coords + g
+            ctx.state.stash.append((coords, dout))
+        return None, dcoords, None, None, None, None   # (no gradient tensor for the anchor: the build node still runs after every lookup)
 
 
 class CorrBlock:
@@ -154,14 +175,20 @@ class CorrBlock:
         """coords [B,2,H,W] (x,y).  Returns [B, L*(2r+1)^2, H, W] contiguous (or [B,H,W,C] when
         channels_last=True, the layout our update block consumes directly).  is_flow=True: the tensor holds the flow and
         the lookup is centred on pixel grid + flow (what the RAFT loop passes: it never forms coords1).  out (channels_last
-        only): a preallocated [B,H,W,C] buffer the lookup writes into (update.MotionBatch's slots)."""
+        only): a preallocated [B,H,W,C] buffer the lookup writes into (update.MotionBatch's slots).
+        Differentiable in `coords` (in the flow when is_flow: the same gradient) when they require grad; detached coordinates
+        run the nodes and launches they always did."""
         coords = coords.float()
         if out is not None and not channels_last:
             raise ValueError("out= is for channels_last lookups")
-        if self._tracks_grad and torch.is_grad_enabled():
+        grad_on = torch.is_grad_enabled()
+        coords_grad = grad_on and coords.requires_grad
+        if self._tracks_grad and grad_on:
             if not self._state.stash:
                 self._state.is_flow = is_flow
-            return _LookupFn.apply(self._anchor, coords.detach(), self, channels_last, is_flow, out)
+            return _LookupFn.apply(self._anchor, coords if coords_grad else coords.detach(), self, channels_last, is_flow, out)
+        if coords_grad:       # feature maps without gradient: the same node without an anchor, for the coordinate gradient alone
+            return _LookupFn.apply(None, coords, self, channels_last, is_flow, out)
         res = ops.corr_lookup_tiled_fwd(self._vol, self._lay, coords, self.radius, is_flow, out=out)
         return res if channels_last else ops.nhwc_to_nchw(res)
 
@@ -227,7 +254,10 @@ class AlternateCorrBlock:
     N x N volume.  One fused launch per lookup (all levels, channels-last, scaled); the backward the reference compiled but
     never wired is live here: lookups only stash (coords, dOut), the feature gradients are formed once per step from
     chunks of the gradient volume (no O(N^2) buffer, no atomics).  alt_cuda_corr.forward / .backward themselves (one
-    level per call, the extension's signature) are in flow_supervisor_amd/alt_cuda_corr.py."""
+    level per call, the extension's signature) are in flow_supervisor_amd/alt_cuda_corr.py.
+    The coordinates get no gradient from these lookups (they are detached here; coordinates that require grad come back with
+    grad None): the reference's extension returns an all-zero coords_grad (alt_cuda_corr/correlation_kernel.cu:307).  CorrBlock
+    is the block that differentiates in the coordinates."""
 
     @on_tensor_device
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):

@@ -11,8 +11,9 @@
 // lane has ~50 loads in flight), then blends out of LDS.  Taps outside the level read
 // as zero.  Algorithmic HBM bytes per query: L*(2r+2)^2*4 read + 8 coords + L*(2r+1)^2*4 out.
 //
-// Backward: coords are detached in the caller (core/raft.py:123), so only dV is
-// produced.  Each query owns its slice of V, so dV accumulation across the 12
+// Backward: only dV is produced here (the loops detach the coordinates, core/raft.py:123;
+// the gradient w.r.t. coordinates that do require grad is fsraft_corr_lookup_dcoords,
+// corr_dcoords.hip).  Each query owns its slice of V, so dV accumulation across the 12
 // iterations is a plain read-modify-write, no atomics.
 #include "common.hpp"
 

@@ -261,6 +261,49 @@ def corr_lookup_tiled_fwd(vol, lay, coords, radius, is_flow=False, out=None):
     return out
 
 
+def corr_lookup_tiled_dcoords(vol, lay, coords, dout, radius, is_flow=False):
+    """-> [B,2,H,W]: gradient of corr_lookup_tiled_fwd w.r.t. `coords` (w.r.t. the flow when is_flow: the same numbers) for the
+    output gradient dout [B,H,W,L*(2r+1)^2] channels-last.  Every element is written; positions whose windows miss the pyramid get 0."""
+    L.require_cuda_f32(vol, coords, dout)
+    B, _, H, W = coords.shape
+    ch = lay.nlev * (2 * radius + 1) ** 2
+    if tuple(dout.shape) != (B, H, W, ch):
+        raise ValueError(f"lookup dout must be [{B},{H},{W},{ch}] channels-last, got {tuple(dout.shape)}")
+    dout = dout.contiguous()
+    bs, cs, ps = _planar2_strides(coords)
+    dc = torch.empty(B, 2, H, W, device=coords.device, dtype=torch.float32)
+    t = TIMER
+    e0 = t.begin() if t else None
+    L.check(_lib().fsraft_corr_lookup_tiled_dcoords(L.ptr(vol), lay.nlev, L.ptr(coords), bs, cs, ps, L.ptr(dout), L.ptr(dc), 2 * H * W,
+                                                    H * W, 1, B, H, W, radius, int(is_flow), L.stream()), "corr_lookup_tiled_dcoords")
+    if t:   # per query: the forward's windows and coords in, dOut in instead of out, two floats out
+        t.end("corr_lookup_dcoords", e0, 0.0, 4.0 * B * H * W * (lay.nlev * (2 * radius + 2) ** 2 + 2 + ch + 2))
+    return dc
+
+
+def corr_lookup_dcoords(levels, coords, dout, radius, nhwc=False):
+    """The same on row-major floor-sized levels [B*H*W, 1, h_l, w_l]; dout [B,CH,H,W], or [B,H,W,CH] when nhwc."""
+    L.require_cuda_f32(coords, dout, *levels)
+    B, _, H, W = coords.shape
+    ch = len(levels) * (2 * radius + 1) ** 2
+    if tuple(dout.shape) != ((B, H, W, ch) if nhwc else (B, ch, H, W)):
+        raise ValueError(f"lookup dout has shape {tuple(dout.shape)} for {ch} channels at {B}x{H}x{W} (nhwc={nhwc})")
+    if [tuple(lv.shape[-2:]) for lv in levels] != pyramid_sizes(H, W, len(levels)):
+        raise ValueError("corr_lookup_dcoords takes floor-sized pyramid levels")
+    dout = dout.contiguous()
+    levels = [lv.contiguous() for lv in levels]
+    bs, cs, ps = _planar2_strides(coords)
+    dc = torch.empty(B, 2, H, W, device=coords.device, dtype=torch.float32)
+    pp, keep = L.ptr_array(levels)
+    t = TIMER
+    e0 = t.begin() if t else None
+    L.check(_lib().fsraft_corr_lookup_dcoords(pp, len(levels), L.ptr(coords), bs, cs, ps, L.ptr(dout), int(nhwc), L.ptr(dc), 2 * H * W,
+                                              H * W, 1, B, H, W, radius, L.stream()), "corr_lookup_dcoords")
+    if t:
+        t.end("corr_lookup_dcoords", e0, 0.0, 4.0 * B * H * W * (len(levels) * (2 * radius + 2) ** 2 + 2 + ch + 2))
+    return dc
+
+
 def corr_dvol_build(douts, coords, lay, B, radius, records=False, is_flow=False, q0=0, nq=0, wmask=None, out=None):
     """Gradient volume [B*H*W, P] of all stashed lookups (douts[t]: [B,H,W,CH] channels-last, coords[t]: [B,2,H,W]);
     records=True: rows of [32 hi | 32 lo] bf16 records (the operand format of gemm_rec_nt / gemm_rec_tn).

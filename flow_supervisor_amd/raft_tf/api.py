@@ -78,23 +78,32 @@ class _PyramidFn(torch.autograd.Function):
 
 
 class _LookupFn(torch.autograd.Function):
-    """Radius-r lookup on row-major levels; backward scatters dOut into zero-initialised level gradients (fsraft_corr_lookup_bwd).
-    No gradient for the coordinates: the RAFT loops stop it (raft/__init__.py: tf.stop_gradient(coords1); pytorch raft.py:122)."""
+    """Radius-r lookup on row-major levels; backward scatters dOut into zero-initialised level gradients (fsraft_corr_lookup_bwd)
+    where the pyramid takes a gradient, and gathers the coordinate gradient (fsraft_corr_lookup_dcoords) where the coordinates do
+    -- a GradientTape that watches them; the RAFT loops stop it (raft/__init__.py: tf.stop_gradient(coords1); pytorch raft.py:122).
+    The levels are kept for the backward only in the second case."""
 
     @staticmethod
     def forward(ctx, coords, radius, *levels):
         B, H, W, _ = coords.shape
         c = coords.permute(0, 3, 1, 2).float()
-        ctx.save_for_backward(c)
+        levels = [lv.contiguous() for lv in levels]
         ctx.radius, ctx.shapes = radius, [tuple(lv.shape) for lv in levels]
-        return ops.corr_lookup_fwd([lv.contiguous() for lv in levels], c, radius, nhwc=True)
+        ctx.save_for_backward(c, *(levels if ctx.needs_input_grad[0] else ()))
+        return ops.corr_lookup_fwd(levels, c, radius, nhwc=True)
 
     @staticmethod
     def backward(ctx, g):
-        (c,) = ctx.saved_tensors
-        dl = [torch.zeros(sh, device=g.device, dtype=torch.float32) for sh in ctx.shapes]
-        ops.corr_lookup_bwd_(dl, c, g.contiguous(), ctx.radius, nhwc=True)
-        return (None, None) + tuple(dl)
+        c, levels = ctx.saved_tensors[0].detach(), [lv.detach() for lv in ctx.saved_tensors[1:]]
+        g = g.contiguous()
+        dl = [None] * len(ctx.shapes)
+        if any(ctx.needs_input_grad[2:]):
+            dl = [torch.zeros(sh, device=g.device, dtype=torch.float32) for sh in ctx.shapes]
+            ops.corr_lookup_bwd_(dl, c, g, ctx.radius, nhwc=True)
+        dc = None
+        if ctx.needs_input_grad[0]:
+            dc = ops.corr_lookup_dcoords(levels, c, g, ctx.radius, nhwc=True).permute(0, 2, 3, 1)
+        return (dc, None) + tuple(dl)
 
 
 def calc_all_field(a, b, num_pool=0):
@@ -159,8 +168,8 @@ class CorrBlock:
         same = any(tuple(lv.shape[-2:]) != (h2 >> l, w2 >> l) for l, lv in enumerate(corr_pyramid))    # TF 'SAME' (ceil) sizes
         if same:
             _same_is_forward_only("CorrBlock.__call__", *corr_pyramid)
-        elif _wants_grad(*corr_pyramid):
-            return _LookupFn.apply(coords.detach(), self.radius, *levels)
+        elif _wants_grad(coords, *corr_pyramid):      # (coordinates that require grad get theirs, also from a detached pyramid)
+            return _LookupFn.apply(coords, self.radius, *levels)
         c = coords.permute(0, 3, 1, 2)                       # NCHW view of the NHWC coords: strides, no copy
         return ops.corr_lookup_fwd(levels, c.float(), self.radius, nhwc=True, same=same)
 

@@ -76,6 +76,14 @@ int fsraft_corr_build_rec(const void* f1r, const void* f2r, float* vol, int num_
  * pytorch/core/raft.py:121-131, never materialised) */
 int fsraft_corr_lookup_tiled_fwd(const float* vol, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs,
                                  int64_t coords_ps, float* out, int B, int H, int W, int radius, int add_grid, hipStream_t stream);
+/* d (lookup) / d coords (grid_sampler_2d_backward w.r.t. the grid): dcoords element (b,c,pix) written at
+ * dcoords[b*dbs + c*dcs + pix*dps] -- every element, never accumulated; dout [B,H,W,CH] channels-last.  At integer positions
+ * the slope is that of the cell to the right / below; taps outside a level are zero and the jump to zero is part of the slope;
+ * positions whose window misses a level contribute 0.  With add_grid this is also the gradient w.r.t. the flow.  Enqueues
+ * only; radius 3 or 4, num_levels 1..4, B*H*W < 2^31, else FSRAFT_ERR_ARG and nothing is written. */
+int fsraft_corr_lookup_tiled_dcoords(const float* vol, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs,
+                                     int64_t coords_ps, const float* dout, float* dcoords, int64_t dbs, int64_t dcs, int64_t dps,
+                                     int B, int H, int W, int radius, int add_grid, hipStream_t stream);
 /* Gradient volume of n lookups at once (grid_sampler_2d_backward w.r.t. the volume, pytorch/core/utils/utils.py:57-71, for
  * all iterations of a step): dvol [B*H*W][P] = (or +=, accumulate != 0) sum_t (d out_t / d V)^T dout_t, pad cells zero;
  * dout[t] is [B,H,W,CH] channels-last, coords[t] element (b, c, pix) at coords[t][b*s0 + c*s1 + pix*s2] with
@@ -116,6 +124,11 @@ int fsraft_corr_lookup_fwd(float* const* levels, int num_levels, const float* co
 int fsraft_corr_lookup_bwd(float* const* dlevels, int num_levels, const float* coords, int64_t coords_bs,
                            int64_t coords_cs, int64_t coords_ps, const float* dout, int nhwc_in, int B, int H, int W,
                            int radius, hipStream_t stream);
+/* fsraft_corr_lookup_tiled_dcoords on row-major levels[l] [B*H*W, 1, H >> l, W >> l]; dout [B,CH,H,W], or [B,H,W,CH] when
+ * nhwc_in != 0.  num_levels 1..4. */
+int fsraft_corr_lookup_dcoords(float* const* levels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs,
+                               int64_t coords_ps, const float* dout, int nhwc_in, float* dcoords, int64_t dbs, int64_t dcs,
+                               int64_t dps, int B, int H, int W, int radius, hipStream_t stream);
 
 /* ---- memory-efficient correlation (no N x N volume) ----------------------------------
  * Replaces alt_cuda_corr.forward / .backward, pytorch/alt_cuda_corr/correlation.cpp:23-54

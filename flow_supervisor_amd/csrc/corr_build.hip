@@ -638,10 +638,13 @@ __global__ __launch_bounds__(256) void corr_pool_same_kernel(const float* __rest
 // flow at raft/semi.py:250-251, 257-258.
 extern "C" int fsraft_corr_pool_pyramid(float* const* levels, int num_levels, int64_t rows, int H2, int W2, hipStream_t stream) {
   if (!levels || num_levels < 1 || num_levels > 8 || rows < 1 || H2 < 1 || W2 < 1) return FS_ERR_ARG;
+  if (!levels[0]) return FS_ERR_ARG;
+  // every level is checked before the first launch: a refused call writes nothing
+  for (int l = 1; l < num_levels; ++l)
+    if (!levels[l] || (H2 >> l) < 1 || (W2 >> l) < 1) return FS_ERR_ARG;
   int h = H2, w = W2;
   for (int l = 1; l < num_levels; ++l) {
     const int h2 = h / 2, w2 = w / 2;
-    if (!levels[l - 1] || !levels[l] || h2 < 1 || w2 < 1) return FS_ERR_ARG;
     int64_t blocks = (rows * h2 * w2 + 255) / 256;
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(corr_pool_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, levels[l - 1], levels[l], rows, h, w, h2, w2);
@@ -753,8 +756,9 @@ extern "C" int fsraft_corr_unpool_bwd(float* const* dlevels, int num_levels, int
 // averaged over their in-range elements.  Equals fsraft_corr_pool_pyramid (to rounding) when H2 and W2 divide by 2^(L-1).
 extern "C" int fsraft_corr_pool_pyramid_same(float* const* levels, int num_levels, int64_t rows, int H2, int W2, hipStream_t stream) {
   if (!levels || num_levels < 1 || num_levels > 8 || rows < 1 || H2 < 1 || W2 < 1 || !levels[0]) return FS_ERR_ARG;
-  for (int l = 1; l < num_levels; ++l) {
+  for (int l = 1; l < num_levels; ++l)      // (before the first launch: a refused call writes nothing)
     if (!levels[l]) return FS_ERR_ARG;
+  for (int l = 1; l < num_levels; ++l) {
     const int k = 1 << l, h2 = (H2 + k - 1) / k, w2 = (W2 + k - 1) / k;
     int64_t blocks = (rows * h2 * w2 + 255) / 256;
     if (blocks > 65536) blocks = 65536;

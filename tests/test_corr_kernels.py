@@ -1,7 +1,7 @@
 """The forward kernels of csrc/corr_build.hip (volume + pyramid builds, pool kernels), lookup_tiled_fwd_kernel of csrc/corr_tiled.hip and
 the forward kernels of csrc/corr_lookup.hip, called through their C entry points, every element against the float64 restatements of
 tests/_corrref.py at the edges of their launch geometry.  The test owns every buffer (_util.Buf: guard rows, unwritten outputs and
-the pad cells of hand-made volumes hold a NaN pattern) and compares the inputs bit for bit afterwards.  Needs an MI355X: -m gpu.
+the pad cells of hand-made volumes hold a NaN pattern) and compares the inputs bit for bit afterwards.  Needs an MI355X: -m gpu.  The backward kernels: tests/test_corr_bwd_kernels.py.
 
 Build (_corrref.BUILD_SHAPES: 1x1 with C = 2, 3x5, 8x8 down to 1x1, 9x17, 10x14, 8x33, 15x17 / 16x16 / 1x257 = 255 / 256 / 257
 queries, 2 x 13x22; C in {2, 14, 16, 18, 34}, records C in {32, 64, 96, 256}; gaussian maps, one sample scaled by 2^10 / 2^-10, a

@@ -20,8 +20,10 @@ reference's grid_sample is.  The RAFT / L2L / GMA loops detach them (raft.py:123
 exactly the nodes and launches they always did; a caller whose ``coords`` require grad
 gets ``coords.grad`` from fsraft_corr_lookup_tiled_dcoords (csrc/corr_dcoords.hip), one
 gather per lookup, also from a block whose feature maps take no gradient.  First
-derivatives only.  ``AlternateCorrBlock`` gives the coordinates no gradient: the
+derivatives only.  ``AlternateCorrBlock`` gives the coordinates no gradient by default: the
 reference's extension returns an all-zero coords_grad there (correlation_kernel.cu:307).
+``AlternateCorrBlock(..., coords_grad=True)`` gives the same gradient as ``CorrBlock`` from
+fsraft_altcorr_fused_dcoords (csrc/altcorr_dcoords.hip), still without the volume.
 """
 import math
 
@@ -204,13 +206,15 @@ class CorrBlock:
 class _AltBuildFn(torch.autograd.Function):
     """(fmap1, fmap2) -> anchor.  Forward does nothing; backward -- reached once every lookup of the step has handed in its
     (coords, dOut) -- runs the volume backward a chunk of queries at a time (ops.corr_bwd_chunked): the gradient volume of
-    `chunk` queries, two record GEMMs, no O(N^2) buffer and no atomics on the feature gradients."""
+    `chunk` queries, two record GEMMs, no O(N^2) buffer and no atomics on the feature gradients.  fixed_order (a block built
+    with coords_grad=True): the GEMMs' k-slices are added in an order that does not depend on timing, so that the feature
+    gradients are the same bits whether or not a lookup's coordinates take a gradient."""
 
     @staticmethod
-    def forward(ctx, fmap1, fmap2, state, num_levels, radius):
+    def forward(ctx, fmap1, fmap2, state, num_levels, radius, fixed_order=False):
         # (the node holds the block's STATE, not the block: block -> anchor -> grad_fn -> ctx -> block would be a reference cycle
         #  that keeps the feature records and the pooled pyramid waiting for the cyclic collector, 32 MB per step at 2 x 32x48)
-        ctx.state, ctx.num_levels, ctx.radius = state, num_levels, radius
+        ctx.state, ctx.num_levels, ctx.radius, ctx.fixed_order = state, num_levels, radius, fixed_order
         ctx.save_for_backward(fmap1, fmap2)
         ctx.set_materialize_grads(False)
         return ops.zeros(1, device=fmap1.device)
@@ -221,32 +225,46 @@ class _AltBuildFn(torch.autograd.Function):
         st = ctx.state
         stash, st.stash = st.stash, []
         if not stash:
-            return torch.zeros_like(fmap1), torch.zeros_like(fmap2), None, None, None
+            return torch.zeros_like(fmap1), torch.zeros_like(fmap2), None, None, None, None
         lay = ops.VolLayout.get(fmap1.shape[2], fmap1.shape[3], ctx.num_levels)
         d1, d2 = ops.corr_bwd_chunked(fmap1, fmap2, [d for _, d in stash], [c for c, _ in stash], lay, ctx.radius,
-                                      is_flow=st.is_flow)
-        return d1, d2, None, None, None
+                                      is_flow=st.is_flow, fixed_order=ctx.fixed_order)
+        return d1, d2, None, None, None, None
 
 
 class _AltLookupFn(torch.autograd.Function):
+    """One lookup of AlternateCorrBlock.  anchor: the build node's 1-element output (None for a block whose feature maps take no
+    gradient: the node then exists for the coordinate gradient alone, AlternateCorrBlock(coords_grad=True)).  Backward hands
+    (coords, dOut) to the block's state for the chunked feature backward; when `coords` requires grad it also returns
+    ops.altcorr_fused_dcoords(...), computed from the channels-last maps the forward read.  Only in that case the node keeps
+    those tensors (not the block: see the reference-cycle note in _AltBuildFn)."""
+
     @staticmethod
     def forward(ctx, anchor, coords, block, channels_last, is_flow, out_buf=None):
         out = ops.altcorr_fused_fwd(block._f1, block._f2, coords, block.radius, is_flow, recs=block._recs, out=out_buf)
-        ctx.state, ctx.cl, ctx.is_flow = block._state, channels_last, is_flow
+        ctx.state = block._state if anchor is not None else None
+        ctx.cl, ctx.is_flow = channels_last, is_flow
+        if ctx.needs_input_grad[1]:
+            ctx.f1, ctx.f2, ctx.radius = block._f1, list(block._f2), block.radius
         ctx.save_for_backward(coords)
         return out if channels_last else ops.nhwc_to_nchw(out)
 
     @staticmethod
     def backward(ctx, dout):
-        (coords,) = ctx.saved_tensors
+        coords = ctx.saved_tensors[0].detach()
         st = ctx.state
         dout = dout.contiguous() if ctx.cl else ops.nchw_to_nhwc(dout)
-        if ctx.is_flow != st.is_flow:
-            B, _, H, W = coords.shape
-            g = coords_grid(B, H, W, device=coords.device)
-            coords = coords - g if st.is_flow else coords + g
-        st.stash.append((coords, dout))
-        return None, None, None, None, None, None
+        dcoords = None
+        if ctx.needs_input_grad[1]:
+            dcoords = ops.altcorr_fused_dcoords(ctx.f1, ctx.f2, coords, dout, ctx.radius, ctx.is_flow)
+            ctx.f1 = ctx.f2 = None
+        if st is not None:
+            if ctx.is_flow != st.is_flow:
+                B, _, H, W = coords.shape
+                g = coords_grid(B, H, W, device=coords.device)
+                coords = coords - g if st.is_flow else coords + g
+            st.stash.append((coords, dout))
+        return None, dcoords, None, None, None, None
 
 
 class AlternateCorrBlock:
@@ -255,23 +273,33 @@ class AlternateCorrBlock:
     never wired is live here: lookups only stash (coords, dOut), the feature gradients are formed once per step from
     chunks of the gradient volume (no O(N^2) buffer, no atomics).  alt_cuda_corr.forward / .backward themselves (one
     level per call, the extension's signature) are in flow_supervisor_amd/alt_cuda_corr.py.
-    The coordinates get no gradient from these lookups (they are detached here; coordinates that require grad come back with
-    grad None): the reference's extension returns an all-zero coords_grad (alt_cuda_corr/correlation_kernel.cu:307).  CorrBlock
-    is the block that differentiates in the coordinates."""
+    coords_grad (extension, default False).  False: the coordinates get no gradient from these lookups (they are detached here;
+    coordinates that require grad come back with grad None), as the reference's extension returns an all-zero coords_grad
+    (alt_cuda_corr/correlation_kernel.cu:307).  True: a lookup whose coordinates (or flow, with is_flow: the same numbers)
+    require grad is differentiable in them -- the gradient CorrBlock gives, from fsraft_altcorr_fused_dcoords
+    (csrc/altcorr_dcoords.hip): one gather over the feature rows the forward read, still without the volume, also from a block
+    whose feature maps take no gradient.  First derivatives only.  Detached coordinates (the RAFT / L2L loops) run the nodes
+    they always did under either setting.  Such a block also promises that asking for the coordinate gradient does not change
+    the feature gradients by a bit: its feature backward adds the k-slices of its GEMMs in a fixed order
+    (ops.corr_bwd_chunked(fixed_order=True): fewer slices, slower), where the default block's adds them as they arrive and two
+    runs of one graph differ in the last bit."""
 
     @on_tensor_device
-    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4, coords_grad=False):
         if not 1 <= num_levels <= 4:
             raise NotImplementedError("the HIP correlation kernels are built for 1..4 pyramid levels")
         if fmap1.shape[1] % 4 != 0:
             raise NotImplementedError("the HIP alt-corr kernels need a channel count that is a multiple of 4")
+        if coords_grad and (radius not in (3, 4) or fmap1.shape[1] > 256):
+            raise NotImplementedError("the HIP coordinate gradient of the alt-corr lookup is built for radius 3 and 4 and up to 256 channels")
         self.num_levels = num_levels
         self.radius = radius
+        self.coords_grad = bool(coords_grad)
         fmap1 = fmap1.float()
         fmap2 = fmap2.float()
         self._state = _GradState(fmap1.device)
         self._tracks_grad = torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad)
-        self._anchor = _AltBuildFn.apply(fmap1, fmap2, self._state, num_levels, radius) if self._tracks_grad else None
+        self._anchor = _AltBuildFn.apply(fmap1, fmap2, self._state, num_levels, radius, self.coords_grad) if self._tracks_grad else None
         with torch.no_grad():
             self.pyramid = [(fmap1, fmap2)]
             f1, f2 = fmap1, fmap2
@@ -294,9 +322,13 @@ class AlternateCorrBlock:
         coords = coords.float()
         if out is not None and not channels_last:
             raise ValueError("out= is for channels_last lookups")
-        if self._tracks_grad and torch.is_grad_enabled():
+        grad_on = torch.is_grad_enabled()
+        coords_grad = self.coords_grad and grad_on and coords.requires_grad
+        if self._tracks_grad and grad_on:
             if not self._state.stash:
                 self._state.is_flow = is_flow
-            return _AltLookupFn.apply(self._anchor, coords.detach(), self, channels_last, is_flow, out)
+            return _AltLookupFn.apply(self._anchor, coords if coords_grad else coords.detach(), self, channels_last, is_flow, out)
+        if coords_grad:       # feature maps without gradient: the same node without an anchor, for the coordinate gradient alone
+            return _AltLookupFn.apply(None, coords, self, channels_last, is_flow, out)
         res = ops.altcorr_fused_fwd(self._f1, self._f2, coords, self.radius, is_flow, recs=self._recs, out=out)
         return res if channels_last else ops.nhwc_to_nchw(res)

@@ -141,7 +141,7 @@ class L2L(RAFT):
                     early = uncropped(image1.shape[0])
         fmap1, fmap2 = features(image1, image2)
         if self.args.alternate_corr:
-            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
+            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, coords_grad=getattr(self.args, "alt_coords_grad", False))
         else:
             corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
         if early is not None:

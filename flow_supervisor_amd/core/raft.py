@@ -112,7 +112,7 @@ class RAFT(nn.Module):
             fmap1, fmap2 = self.fnet([image1, image2])
         fmap1, fmap2 = fmap1.float(), fmap2.float()
         if self.args.alternate_corr:
-            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
+            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, coords_grad=getattr(self.args, "alt_coords_grad", False))
         else:
             corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
         if overlap:

@@ -76,28 +76,6 @@ struct RowWindows {            // row-major levels: lane = (window row, quarter 
   }
 };
 
-struct Grad2 {      // where dcoords element (b, c, pix) goes
-  float* p;
-  int64_t bs, cs, ps;
-};
-
-// sum over the 64 lanes, the same value in every lane, always added in the same order: quads, halves of a row, rows (DPP), then
-// the four rows of 16 lanes left to right
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_fixed(float v) {
-  v += dpp_move<0xB1>(v);       // quad_perm [1, 0, 3, 2]
-  v += dpp_move<0x4E>(v);       // quad_perm [2, 3, 0, 1]
-  v += dpp_move<0x141>(v);      // row_half_mirror
-  v += dpp_move<0x140>(v);      // row_mirror
-  const int iv = __builtin_bit_cast(int, v);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(iv, 48));
-  return ((r0 + r1) + r2) + r3;
-}
-
 template <int R>
 struct DoutLoad {
   float g[4][TL<R>::ROUNDS];

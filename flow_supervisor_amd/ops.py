@@ -416,12 +416,16 @@ def f2cat_records(fmap2, lay):
     return to_records(f2cat)
 
 
-def corr_bwd_chunked(fmap1, fmap2, douts, coords, lay, radius, is_flow=False, chunk=2048, f1r=None):
+def corr_bwd_chunked(fmap1, fmap2, douts, coords, lay, radius, is_flow=False, chunk=2048, f1r=None, fixed_order=False):
     """Backward of volume + lookups WITHOUT an O(N^2) buffer (AlternateCorrBlock's contract, pytorch/core/corr.py:63-91): the
     gradient volume exists for `chunk` queries at a time (chunk x P floats, records), and every chunk feeds the same two
-    record GEMMs as the dense path: dF1[:, chunk] = s * f2cat . dV^T and d2cat += s * dV^T . f1[chunk].  (dfmap1, dfmap2) NCHW."""
+    record GEMMs as the dense path: dF1[:, chunk] = s * f2cat . dV^T and d2cat += s * dV^T . f1[chunk].  (dfmap1, dfmap2) NCHW.
+    The GEMMs add their k-slices with fp32 atomics: 8 and 3 slices arrive in any order, and two runs differ in the last bit.
+    fixed_order: 2 slices onto zeros (a + b = b + a) and 1 slice per chunk onto d2cat (one add per element and launch, the
+    launches in stream order), so two runs give the same bits -- at 1 x 47x156, 12 lookups, 966 us instead of 602 us."""
     B, C, H, W = fmap1.shape
     N, P = H * W, lay.P
+    nt_slices, tn_slices = (2, 1) if fixed_order else (8, 3)
     s = 1.0 / math.sqrt(C)
     tm = TIMER
     e0 = tm.begin() if tm else None
@@ -438,7 +442,7 @@ def corr_bwd_chunked(fmap1, fmap2, douts, coords, lay, radius, is_flow=False, ch
             # (CHUNK_KSKIP, off: as in the dense path the two GEMMs can visit only the k-tiles the chunk's lookups reached -- measured
             #  at 1 x 47x156 in 2048-query chunks: the gradient rows 0.263 -> 0.227 ms, but the per-chunk pre-pass and the short GEMMs'
             #  fixed costs take more than the skipped k-tiles give back, 0.784 -> 0.889 ms)
-            kt = corr_bwd_ktiles(coords, lay, B, radius, is_flow, q0=b * N + i0, nq=n) if (BWD_KSKIP and CHUNK_KSKIP) else None
+            kt = corr_bwd_ktiles(coords, lay, B, radius, is_flow, q0=b * N + i0, nq=n) if (BWD_KSKIP and CHUNK_KSKIP and not fixed_order) else None
             dV = corr_dvol_build(douts, coords, lay, B, radius, records=True, is_flow=is_flow, q0=b * N + i0, nq=n,
                                  wmask=kt.wmask if (kt is not None and DVOL_WMASK) else None)
             a_nt = (ctypes.c_void_p(f2r.data_ptr() + b * C * P * 4), P, 0, L.ptr(dV), P, 0,
@@ -450,9 +454,9 @@ def corr_bwd_chunked(fmap1, fmap2, douts, coords, lay, radius, is_flow=False, ch
                 L.check(lib.fsraft_gemm_rec_tn_list(*a_tn, 3, 1, L.ptr(kt.tn_list), L.ptr(kt.tn_count), kt.tn_stride, 0, L.stream()), "gemm_rec_tn_list")
             else:
                 # d1[b][:, i0:i0+n] = s * f2cat[b] [C x P] . dV [n x P]^T
-                L.check(lib.fsraft_gemm_rec_nt(*a_nt, 8, 0, L.stream()), "gemm_rec_nt")
+                L.check(lib.fsraft_gemm_rec_nt(*a_nt, nt_slices, 0, L.stream()), "gemm_rec_nt")
                 # d2cat[b] [P x C] += s * dV [n x P]^T . f1[b][i0:i0+n] [n x C]
-                L.check(lib.fsraft_gemm_rec_tn(*a_tn, 3, 1, L.stream()), "gemm_rec_tn")
+                L.check(lib.fsraft_gemm_rec_tn(*a_tn, tn_slices, 1, L.stream()), "gemm_rec_tn")
     d2 = torch.empty(B, H, W, C, device=fmap1.device, dtype=torch.float32)
     L.check(lib.fsraft_corr_dfmap2(L.ptr(d2cat), L.ptr(d2), lay.nlev, B, C, H, W, L.stream()), "corr_dfmap2")
     out = d1.view(B, C, H, W), nhwc_to_nchw(d2, C)
@@ -494,6 +498,38 @@ def altcorr_fused_fwd(f1_cl, f2_levels, coords, radius, is_flow=False, recs=None
         t.end("altcorr_fwd", e0, 2.0 * B * H * W * nl * (2 * radius + 2) ** 2 * C,
               4.0 * B * (H * W * C + sum(f.shape[1] * f.shape[2] for f in f2_levels) * C + H * W * (2 + out.shape[-1])))
     return out
+
+
+def altcorr_fused_dcoords(f1_cl, f2_levels, coords, dout, radius, is_flow=False):
+    """-> [B,2,H,W]: gradient of altcorr_fused_fwd w.r.t. `coords` (w.r.t. the flow when is_flow: the same numbers) for the output
+    gradient dout [B,H,W,L*(2r+1)^2] channels-last, from the feature maps alone (csrc/altcorr_dcoords.hip; fp32 in either
+    arithmetic mode).  Every element is written; positions whose windows miss the maps get 0."""
+    L.require_cuda_f32(f1_cl, coords, dout, *f2_levels)
+    if f1_cl.dim() != 4 or coords.dim() != 4:
+        raise ValueError("altcorr_fused_dcoords takes fmap1 [B,H,W,C] channels-last and coords [B,2,H,W]")
+    B, H, W, C = f1_cl.shape
+    nl = len(f2_levels)
+    ch = nl * (2 * radius + 1) ** 2
+    if tuple(coords.shape) != (B, 2, H, W):
+        raise ValueError(f"coords must be [{B},2,{H},{W}], got {tuple(coords.shape)}")
+    if tuple(dout.shape) != (B, H, W, ch):
+        raise ValueError(f"lookup dout must be [{B},{H},{W},{ch}] channels-last, got {tuple(dout.shape)}")
+    if [tuple(f.shape) for f in f2_levels] != [(B, h, w, C) for h, w in pyramid_sizes(H, W, nl)]:
+        raise ValueError(f"fmap2 levels must be [{B},H>>l,W>>l,{C}] channels-last, got {[tuple(f.shape) for f in f2_levels]}")
+    if not (f1_cl.is_contiguous() and all(f.is_contiguous() for f in f2_levels)):
+        raise ValueError("altcorr_fused_dcoords takes contiguous channels-last feature maps")
+    dout = dout.contiguous()
+    bs, cs, ps = _planar2_strides(coords)
+    dc = torch.empty(B, 2, H, W, device=coords.device, dtype=torch.float32)
+    pp, keep = L.ptr_array(f2_levels)
+    t = TIMER
+    e0 = t.begin() if t else None
+    L.check(_lib().fsraft_altcorr_fused_dcoords(L.ptr(f1_cl), pp, nl, L.ptr(coords), bs, cs, ps, int(is_flow), L.ptr(dout), L.ptr(dc),
+                                                2 * H * W, H * W, 1, B, H, W, C, radius, L.stream()), "altcorr_fused_dcoords")
+    if t:   # the forward's compulsory bytes with dOut read in place of out written, plus two floats; two FMAs per position and channel
+        t.end("altcorr_dcoords", e0, 4.0 * B * H * W * nl * (2 * radius + 2) ** 2 * C,
+              4.0 * B * (H * W * C + sum(f.shape[1] * f.shape[2] for f in f2_levels) * C + H * W * (2 + ch + 2)))
+    return dc
 
 
 def corr_build_bwd_tiled(fmap1, fmap2, dvol, lay, records=False, f1r=None, ktiles=None):

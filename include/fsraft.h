@@ -150,6 +150,18 @@ int fsraft_altcorr_bwd(const float* fmap1, const float* fmap2, const float* coor
 int fsraft_altcorr_fused_fwd(const float* fmap1, const float* const* fmap2_levels, int num_levels, const float* coords,
                              int64_t coords_bs, int64_t coords_cs, int64_t coords_ps, int add_grid, float* out, int B, int H, int W,
                              int C, int radius, hipStream_t stream);
+/* d (that lookup) / d coords, on the volume that is never formed, V_l[q,y,x] = fmap1[q] . fmap2_l[y,x] / sqrt(C) (the reference's
+ * extension returns zeros, alt_cuda_corr/correlation_kernel.cu:307).  fmap1, fmap2_levels, coords and add_grid as
+ * fsraft_altcorr_fused_fwd; dout [B,H,W,L*(2r+1)^2] channels-last; dcoords element (b,c,pix) written at
+ * dcoords[b*dbs + c*dcs + pix*dps] -- every element, never accumulated: the contract of fsraft_corr_lookup_tiled_dcoords (the
+ * cell to the right / below at integer positions, the jump to zero at a level's edge is part of the slope, a level at which
+ * |coords 2^-l| >= 30000 contributes 0).  With num_levels = 1 and a pre-pooled map: the per-level coords_grad the extension
+ * never computed.  fp32 arithmetic, no atomics: two launches give the same bits.  Enqueues only; radius 3 or 4, num_levels
+ * 1..4 (every level at least 1x1), 1 <= C <= 256, B*H*W < 2^31, no null pointer, else FSRAFT_ERR_ARG and nothing is written. */
+int fsraft_altcorr_fused_dcoords(const float* fmap1, const float* const* fmap2_levels, int num_levels, const float* coords,
+                                 int64_t coords_bs, int64_t coords_cs, int64_t coords_ps, int add_grid, const float* dout,
+                                 float* dcoords, int64_t dbs, int64_t dcs, int64_t dps, int B, int H, int W, int C, int radius,
+                                 hipStream_t stream);
 
 /* The same lookup with the dot products of a tile of queries against a region of target rows as one small GEMM on the matrix
  * pipe (bf16x3 on pre-split operands, the arithmetic of the volume build): f1r [B][H*W][C/32 records] and f2r_levels[l]

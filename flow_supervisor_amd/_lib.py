@@ -123,6 +123,10 @@ SIGNATURES = {
     "fsraft_corr_pool_pyramid": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_pool_pyramid_same": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_lookup_fwd_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
+    "fsraft_corr_unpool_same_bwd": [_PP, c_int, c_int64, c_int, c_int, _S],
+    "fsraft_corr_lookup_bwd_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
+    "fsraft_corr_lookup_dcoords_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int64,
+                                        c_int, c_int, c_int, c_int, _S],
     "fsraft_set_norm_blocks": [c_int],
     "fsraft_get_tuning": [c_int],
     "fsraft_conv_last_route": [c_int],

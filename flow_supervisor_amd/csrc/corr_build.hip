@@ -601,6 +601,91 @@ __global__ __launch_bounds__(256) void corr_unpool_bwd_vec_kernel(Levels lv, int
   }
 }
 
+// Backward of corr_pool_same_kernel for every level at once, folded into level 0 in place: the transpose of the 'SAME' pooling.
+// Level-0 cell (y, x) lies in exactly one window per level l >= 1 (k = 2^l, the leading padding py, px as in the forward kernel):
+// (Y, X) = ((y + py) >> l, (x + px) >> l), which averaged over its cy x cx in-range cells.  In this order and form:
+//   acc = 0;  for l = 1, 2, ..., nlev - 1:  acc += g_l[Y][X] * (1.0f / (float)(cy cx));   g0[y][x] = g0[y][x] + acc
+// (the weight is the correctly rounded reciprocal of the count, the term its product with the level's gradient).  A gather: every
+// thread writes cells nobody else reads or writes, so two launches give the same bits.  Levels >= 1 are only read.
+struct SameLevels {
+  float* g0;
+  const float* p[8];
+  int h[8], w[8], py[8], px[8];       // entries 1 .. nlev - 1
+};
+
+__device__ __forceinline__ int same_count(int i, int l, int pad, int size) {   // in-range cells of window i along one axis
+  const int lo = (i << l) - pad;
+  return min(lo + (1 << l), size) - max(lo, 0);
+}
+
+// NLEV: the level count at compile time (2, 3, 4), or 0 for the count in nlev_rt; the loops over the levels are unrolled either
+// way, so that every level's load is in flight before the first one is waited for.
+template <int NLEV>
+__global__ __launch_bounds__(256) void corr_unpool_same_bwd_kernel(SameLevels lv, int nlev_rt, int64_t rows, int H, int W) {
+  const int nlev = NLEV ? NLEV : nlev_rt;
+  const int64_t total = rows * H * W;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int x = (int)(e % W);
+    const int64_t t = e / W;
+    const int y = (int)(t % H);
+    const int64_t r = t / H;
+    const float old = lv.g0[e];
+    float g[8];
+#pragma unroll
+    for (int l = 1; l < 8; ++l)
+      if (l < nlev) g[l] = lv.p[l][(r * lv.h[l] + ((y + lv.py[l]) >> l)) * lv.w[l] + ((x + lv.px[l]) >> l)];
+    float acc = 0.f;
+#pragma unroll
+    for (int l = 1; l < 8; ++l)
+      if (l < nlev) {
+        const int cnt = same_count((y + lv.py[l]) >> l, l, lv.py[l], H) * same_count((x + lv.px[l]) >> l, l, lv.px[l], W);
+        acc += g[l] * (1.0f / (float)cnt);
+      }
+    lv.g0[e] = old + acc;
+  }
+}
+
+// W % 4 == 0 and a 16-byte aligned level 0: one thread per 4 consecutive x.  The four need not share a window (W = 12, k = 8: px = 2
+// and x = 4 .. 7 lies in two), but they lie in at most two neighbouring ones: k >= 4 is as long as the vector, and at k = 2 an even
+// W has px = 0.  So both windows' terms are formed once and every element picks its own by its own index.  (Where the second
+// window does not exist no element lies in it; its index is clamped to the last one, so the load stays inside the level.)
+template <int NLEV>
+__global__ __launch_bounds__(256) void corr_unpool_same_bwd_vec_kernel(SameLevels lv, int nlev_rt, int64_t nrows, int H, int W) {
+  const int nlev = NLEV ? NLEV : nlev_rt;
+  const int W4 = W >> 2;
+  const int64_t total = nrows * W4;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int x = (int)(e % W4) * 4;
+    const int64_t row = e / W4;            // = r * H + y
+    const int y = (int)(row % H);
+    const int64_t r = row / H;
+    f32x4* p = reinterpret_cast<f32x4*>(lv.g0 + row * W + x);
+    f32x4 o = *p;
+    float g[8][2];
+#pragma unroll
+    for (int l = 1; l < 8; ++l)
+      if (l < nlev) {
+        const int X0 = (x + lv.px[l]) >> l;
+        const float* gp = lv.p[l] + (r * lv.h[l] + ((y + lv.py[l]) >> l)) * lv.w[l];
+        g[l][0] = gp[X0];
+        g[l][1] = gp[min(X0 + 1, lv.w[l] - 1)];
+      }
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int l = 1; l < 8; ++l)
+      if (l < nlev) {
+        const int px = lv.px[l], X0 = (x + px) >> l;
+        const int cy = same_count((y + lv.py[l]) >> l, l, lv.py[l], H);
+        const float v0 = g[l][0] * (1.0f / (float)(cy * same_count(X0, l, px, W)));
+        const float v1 = g[l][1] * (1.0f / (float)(cy * same_count(min(X0 + 1, lv.w[l] - 1), l, px, W)));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[i] += (((x + i + px) >> l) == X0) ? v0 : v1;
+      }
+    o[0] = o[0] + acc[0]; o[1] = o[1] + acc[1]; o[2] = o[2] + acc[2]; o[3] = o[3] + acc[3];
+    *p = o;
+  }
+}
+
 // dst[row][y][x] = 2x2 average of src[row][2y..][2x..] (floor sizes), the same expression the fused build uses
 __global__ __launch_bounds__(256) void corr_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int64_t rows,
                                                         int h, int w, int h2, int w2) {
@@ -764,5 +849,35 @@ extern "C" int fsraft_corr_pool_pyramid_same(float* const* levels, int num_level
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(corr_pool_same_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, levels[0], levels[l], rows, H2, W2, k);
   }
+  return fs_launch_status();
+}
+
+// In place: dlevels[0] += the transposes of the 'SAME' poolings applied to dlevels[1 ..] (the backward of
+// fsraft_corr_pool_pyramid_same; sizes and padding as there).  dlevels[l] hold dL/dV_l on entry; levels >= 1 are only read.
+extern "C" int fsraft_corr_unpool_same_bwd(float* const* dlevels, int num_levels, int64_t rows, int H2, int W2, hipStream_t stream) {
+  if (!dlevels || num_levels < 1 || num_levels > 8 || rows < 1 || H2 < 1 || W2 < 1) return FS_ERR_ARG;
+  for (int l = 0; l < num_levels; ++l)      // (before the first launch: a refused call writes nothing)
+    if (!dlevels[l]) return FS_ERR_ARG;
+  if (num_levels == 1) return FS_OK;
+  SameLevels lv;
+  lv.g0 = dlevels[0];
+  for (int l = 0; l < 8; ++l) {
+    const int k = 1 << l, h = (H2 + k - 1) / k, w = (W2 + k - 1) / k;
+    lv.p[l] = l < num_levels ? dlevels[l] : nullptr;
+    lv.h[l] = h; lv.w[l] = w;
+    lv.py[l] = (h * k - H2) / 2; lv.px[l] = (w * k - W2) / 2;
+  }
+  const int64_t total = rows * H2 * W2;
+  const bool vec = W2 % 4 == 0 && ((uintptr_t)dlevels[0] % 16) == 0;
+  const int64_t work = vec ? total / 4 : total;
+  const int blocks = (int)((work + 255) / 256 < 8192 ? (work + 255) / 256 : 8192);
+  auto vec_kernel = num_levels == 2 ? corr_unpool_same_bwd_vec_kernel<2> : num_levels == 3 ? corr_unpool_same_bwd_vec_kernel<3> :
+                    num_levels == 4 ? corr_unpool_same_bwd_vec_kernel<4> : corr_unpool_same_bwd_vec_kernel<0>;
+  auto kernel = num_levels == 2 ? corr_unpool_same_bwd_kernel<2> : num_levels == 3 ? corr_unpool_same_bwd_kernel<3> :
+                num_levels == 4 ? corr_unpool_same_bwd_kernel<4> : corr_unpool_same_bwd_kernel<0>;
+  if (vec)
+    hipLaunchKernelGGL(vec_kernel, dim3(blocks), dim3(256), 0, stream, lv, num_levels, rows * H2, H2, W2);
+  else
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, stream, lv, num_levels, rows, H2, W2);
   return fs_launch_status();
 }

@@ -181,6 +181,36 @@ int launch_dcoords(const typename WINDOWS::Src& src, int nlev, const Coords& co,
   return fs_launch_status();
 }
 
+// The body of fsraft_corr_lookup_dcoords and its 'SAME' twin: level l is H >> l x W >> l, or the ceil of H / 2^l x W / 2^l.
+int row_dcoords_entry(float* const* levels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs, int64_t coords_ps,
+                      const float* dout, int nhwc_in, float* dcoords, int64_t dbs, int64_t dcs, int64_t dps, int B, int H, int W,
+                      int radius, bool ceil, hipStream_t stream) {
+  if (!levels || !coords || !dout || !dcoords || B < 1 || H < 1 || W < 1 || (radius != 3 && radius != 4) || num_levels < 1 || num_levels > 4)
+    return FS_ERR_ARG;
+  const int64_t nq = (int64_t)B * H * W;
+  if (nq >= (int64_t)1 << 31 || (int64_t)H * W * 4 >= (int64_t)1 << 31) return FS_ERR_ARG;
+  RowWindows<4>::Src s4;
+  for (int l = 0; l < 4; ++l) {
+    const bool on = l < num_levels;
+    const int h = ceil ? (H + (1 << l) - 1) >> l : H >> l, w = ceil ? (W + (1 << l) - 1) >> l : W >> l;
+    if (on && (!levels[l] || h < 1 || w < 1)) return FS_ERR_ARG;
+    s4.p[l] = on ? levels[l] : levels[0];
+    s4.h[l] = on ? h : 0;
+    s4.w[l] = on ? w : 0;
+  }
+  s4.nlev = num_levels;
+  const int CH = num_levels * (2 * radius + 1) * (2 * radius + 1);
+  const int64_t HW = (int64_t)H * W;
+  const Coords co{coords, coords_bs, coords_cs, coords_ps};
+  const Coords go = nhwc_in ? Coords{dout, HW * CH, 1, CH} : Coords{dout, HW * CH, HW, 1};
+  const Grad2 dc{dcoords, dbs, dcs, dps};
+  if (radius == 4) return launch_dcoords<4, RowWindows<4>>(s4, num_levels, co, go, dc, nq, H * W, 0, stream);
+  RowWindows<3>::Src s3;
+  for (int l = 0; l < 4; ++l) { s3.p[l] = s4.p[l]; s3.h[l] = s4.h[l]; s3.w[l] = s4.w[l]; }
+  s3.nlev = num_levels;
+  return launch_dcoords<3, RowWindows<3>>(s3, num_levels, co, go, dc, nq, H * W, 0, stream);
+}
+
 }  // namespace
 
 // dcoords element (b, c, pix) written at dcoords[b*dbs + c*dcs + pix*dps] (every element, never accumulated); dout
@@ -212,27 +242,15 @@ extern "C" int fsraft_corr_lookup_tiled_dcoords(const float* vol, int num_levels
 extern "C" int fsraft_corr_lookup_dcoords(float* const* levels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs,
                                           int64_t coords_ps, const float* dout, int nhwc_in, float* dcoords, int64_t dbs, int64_t dcs,
                                           int64_t dps, int B, int H, int W, int radius, hipStream_t stream) {
-  if (!levels || !coords || !dout || !dcoords || B < 1 || H < 1 || W < 1 || (radius != 3 && radius != 4) || num_levels < 1 || num_levels > 4)
-    return FS_ERR_ARG;
-  const int64_t nq = (int64_t)B * H * W;
-  if (nq >= (int64_t)1 << 31 || (int64_t)H * W * 4 >= (int64_t)1 << 31) return FS_ERR_ARG;
-  RowWindows<4>::Src s4;
-  for (int l = 0; l < 4; ++l) {
-    const bool on = l < num_levels;
-    if (on && (!levels[l] || (H >> l) < 1 || (W >> l) < 1)) return FS_ERR_ARG;
-    s4.p[l] = on ? levels[l] : levels[0];
-    s4.h[l] = on ? H >> l : 0;
-    s4.w[l] = on ? W >> l : 0;
-  }
-  s4.nlev = num_levels;
-  const int CH = num_levels * (2 * radius + 1) * (2 * radius + 1);
-  const int64_t HW = (int64_t)H * W;
-  const Coords co{coords, coords_bs, coords_cs, coords_ps};
-  const Coords go = nhwc_in ? Coords{dout, HW * CH, 1, CH} : Coords{dout, HW * CH, HW, 1};
-  const Grad2 dc{dcoords, dbs, dcs, dps};
-  if (radius == 4) return launch_dcoords<4, RowWindows<4>>(s4, num_levels, co, go, dc, nq, H * W, 0, stream);
-  RowWindows<3>::Src s3;
-  for (int l = 0; l < 4; ++l) { s3.p[l] = s4.p[l]; s3.h[l] = s4.h[l]; s3.w[l] = s4.w[l]; }
-  s3.nlev = num_levels;
-  return launch_dcoords<3, RowWindows<3>>(s3, num_levels, co, go, dc, nq, H * W, 0, stream);
+  return row_dcoords_entry(levels, num_levels, coords, coords_bs, coords_cs, coords_ps, dout, nhwc_in, dcoords, dbs, dcs, dps, B, H, W,
+                           radius, false, stream);
+}
+
+// The same on the levels of a TensorFlow 'SAME' pyramid: [B*H*W, 1, ceil(H / 2^l), ceil(W / 2^l)].
+extern "C" int fsraft_corr_lookup_dcoords_same(float* const* levels, int num_levels, const float* coords, int64_t coords_bs,
+                                               int64_t coords_cs, int64_t coords_ps, const float* dout, int nhwc_in, float* dcoords,
+                                               int64_t dbs, int64_t dcs, int64_t dps, int B, int H, int W, int radius,
+                                               hipStream_t stream) {
+  return row_dcoords_entry(levels, num_levels, coords, coords_bs, coords_cs, coords_ps, dout, nhwc_in, dcoords, dbs, dcs, dps, B, H, W,
+                           radius, true, stream);
 }

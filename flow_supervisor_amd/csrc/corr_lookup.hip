@@ -402,6 +402,29 @@ bool fill_pyr(Pyr& pyr, float* const* levels, int num_levels, int H, int W, bool
   return true;
 }
 
+// The bodies of the lookup entries; ceil picks the level sizes (fill_pyr), nothing else differs between an entry and its twin.
+int lookup_fwd_entry(float* const* levels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs, int64_t coords_ps,
+                     float* out, int nhwc_out, int B, int H, int W, int radius, bool ceil, hipStream_t stream) {
+  Pyr pyr;
+  if (!coords || !out || B < 1 || !fill_pyr(pyr, levels, num_levels, H, W, ceil)) return FS_ERR_ARG;
+  Coords co{coords, coords_bs, coords_cs, coords_ps};
+  const int64_t nq = (int64_t)B * H * W;
+  if (radius == 4) return dispatch_fwd<4>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
+  if (radius == 3) return dispatch_fwd<3>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
+  return FS_ERR_ARG;
+}
+
+int lookup_bwd_entry(float* const* dlevels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs, int64_t coords_ps,
+                     const float* dout, int nhwc_in, int B, int H, int W, int radius, bool ceil, hipStream_t stream) {
+  Pyr pyr;
+  if (!coords || !dout || B < 1 || !fill_pyr(pyr, dlevels, num_levels, H, W, ceil)) return FS_ERR_ARG;
+  Coords co{coords, coords_bs, coords_cs, coords_ps};
+  const int64_t nq = (int64_t)B * H * W;
+  if (radius == 4) return dispatch_bwd<4>(pick_qb(nhwc_in), pyr, co, dout, nhwc_in, nq, H * W, stream);
+  if (radius == 3) return dispatch_bwd<3>(pick_qb(nhwc_in), pyr, co, dout, nhwc_in, nq, H * W, stream);
+  return FS_ERR_ARG;
+}
+
 }  // namespace
 
 extern "C" int fsraft_set_lookup_qb(int qb) {
@@ -420,26 +443,14 @@ extern "C" int fsraft_set_lookup_qb(int qb) {
 extern "C" int fsraft_corr_lookup_fwd(float* const* levels, int num_levels, const float* coords, int64_t coords_bs,
                                       int64_t coords_cs, int64_t coords_ps, float* out, int nhwc_out, int B, int H,
                                       int W, int radius, hipStream_t stream) {
-  Pyr pyr;
-  if (!coords || !out || B < 1 || !fill_pyr(pyr, levels, num_levels, H, W)) return FS_ERR_ARG;
-  Coords co{coords, coords_bs, coords_cs, coords_ps};
-  const int64_t nq = (int64_t)B * H * W;
-  if (radius == 4) return dispatch_fwd<4>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
-  if (radius == 3) return dispatch_fwd<3>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
-  return FS_ERR_ARG;
+  return lookup_fwd_entry(levels, num_levels, coords, coords_bs, coords_cs, coords_ps, out, nhwc_out, B, H, W, radius, false, stream);
 }
 
 // dlevels[l] += d(out)/d(V_l)^T * dout   (accumulates; caller zeroes dlevels once per step)
 extern "C" int fsraft_corr_lookup_bwd(float* const* dlevels, int num_levels, const float* coords, int64_t coords_bs,
                                       int64_t coords_cs, int64_t coords_ps, const float* dout, int nhwc_in, int B,
                                       int H, int W, int radius, hipStream_t stream) {
-  Pyr pyr;
-  if (!coords || !dout || B < 1 || !fill_pyr(pyr, dlevels, num_levels, H, W)) return FS_ERR_ARG;
-  Coords co{coords, coords_bs, coords_cs, coords_ps};
-  const int64_t nq = (int64_t)B * H * W;
-  if (radius == 4) return dispatch_bwd<4>(pick_qb(nhwc_in), pyr, co, dout, nhwc_in, nq, H * W, stream);
-  if (radius == 3) return dispatch_bwd<3>(pick_qb(nhwc_in), pyr, co, dout, nhwc_in, nq, H * W, stream);
-  return FS_ERR_ARG;
+  return lookup_bwd_entry(dlevels, num_levels, coords, coords_bs, coords_cs, coords_ps, dout, nhwc_in, B, H, W, radius, false, stream);
 }
 
 // Forward lookup on a pyramid whose levels have TensorFlow 'SAME' sizes (level l: ceil(H / 2^l) x ceil(W / 2^l)); everything
@@ -447,11 +458,12 @@ extern "C" int fsraft_corr_lookup_bwd(float* const* dlevels, int num_levels, con
 extern "C" int fsraft_corr_lookup_fwd_same(float* const* levels, int num_levels, const float* coords, int64_t coords_bs,
                                            int64_t coords_cs, int64_t coords_ps, float* out, int nhwc_out, int B, int H,
                                            int W, int radius, hipStream_t stream) {
-  Pyr pyr;
-  if (!coords || !out || B < 1 || !fill_pyr(pyr, levels, num_levels, H, W, true)) return FS_ERR_ARG;
-  Coords co{coords, coords_bs, coords_cs, coords_ps};
-  const int64_t nq = (int64_t)B * H * W;
-  if (radius == 4) return dispatch_fwd<4>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
-  if (radius == 3) return dispatch_fwd<3>(pick_qb(nhwc_out), pyr, co, out, nhwc_out, nq, H * W, stream);
-  return FS_ERR_ARG;
+  return lookup_fwd_entry(levels, num_levels, coords, coords_bs, coords_cs, coords_ps, out, nhwc_out, B, H, W, radius, true, stream);
+}
+
+// fsraft_corr_lookup_bwd onto level gradients of the 'SAME' sizes: the same kernels, which take every level size as an argument.
+extern "C" int fsraft_corr_lookup_bwd_same(float* const* dlevels, int num_levels, const float* coords, int64_t coords_bs,
+                                           int64_t coords_cs, int64_t coords_ps, const float* dout, int nhwc_in, int B,
+                                           int H, int W, int radius, hipStream_t stream) {
+  return lookup_bwd_entry(dlevels, num_levels, coords, coords_bs, coords_cs, coords_ps, dout, nhwc_in, B, H, W, radius, true, stream);
 }

@@ -281,15 +281,21 @@ def corr_lookup_tiled_dcoords(vol, lay, coords, dout, radius, is_flow=False):
     return dc
 
 
-def corr_lookup_dcoords(levels, coords, dout, radius, nhwc=False):
-    """The same on row-major floor-sized levels [B*H*W, 1, h_l, w_l]; dout [B,CH,H,W], or [B,H,W,CH] when nhwc."""
+def same_sizes(H, W, num_levels=4):
+    """Level sizes of the TensorFlow 'SAME' pyramid: ceil(H / 2^l) x ceil(W / 2^l)."""
+    return [(-(-H // (1 << l)), -(-W // (1 << l))) for l in range(num_levels)]
+
+
+def corr_lookup_dcoords(levels, coords, dout, radius, nhwc=False, same=False):
+    """The same on row-major floor-sized levels [B*H*W, 1, h_l, w_l]; dout [B,CH,H,W], or [B,H,W,CH] when nhwc.  same=True: the
+    levels have the TensorFlow 'SAME' (ceil) sizes (fsraft_corr_lookup_dcoords_same)."""
     L.require_cuda_f32(coords, dout, *levels)
     B, _, H, W = coords.shape
     ch = len(levels) * (2 * radius + 1) ** 2
     if tuple(dout.shape) != ((B, H, W, ch) if nhwc else (B, ch, H, W)):
         raise ValueError(f"lookup dout has shape {tuple(dout.shape)} for {ch} channels at {B}x{H}x{W} (nhwc={nhwc})")
-    if [tuple(lv.shape[-2:]) for lv in levels] != pyramid_sizes(H, W, len(levels)):
-        raise ValueError("corr_lookup_dcoords takes floor-sized pyramid levels")
+    if [tuple(lv.shape[-2:]) for lv in levels] != (same_sizes if same else pyramid_sizes)(H, W, len(levels)):
+        raise ValueError("corr_lookup_dcoords takes floor-sized pyramid levels, and ceil-sized ones with same=True")
     dout = dout.contiguous()
     levels = [lv.contiguous() for lv in levels]
     bs, cs, ps = _planar2_strides(coords)
@@ -297,8 +303,9 @@ def corr_lookup_dcoords(levels, coords, dout, radius, nhwc=False):
     pp, keep = L.ptr_array(levels)
     t = TIMER
     e0 = t.begin() if t else None
-    L.check(_lib().fsraft_corr_lookup_dcoords(pp, len(levels), L.ptr(coords), bs, cs, ps, L.ptr(dout), int(nhwc), L.ptr(dc), 2 * H * W,
-                                              H * W, 1, B, H, W, radius, L.stream()), "corr_lookup_dcoords")
+    fn = _lib().fsraft_corr_lookup_dcoords_same if same else _lib().fsraft_corr_lookup_dcoords
+    L.check(fn(pp, len(levels), L.ptr(coords), bs, cs, ps, L.ptr(dout), int(nhwc), L.ptr(dc), 2 * H * W, H * W, 1, B, H, W, radius,
+               L.stream()), "corr_lookup_dcoords")
     if t:
         t.end("corr_lookup_dcoords", e0, 0.0, 4.0 * B * H * W * (len(levels) * (2 * radius + 2) ** 2 + 2 + ch + 2))
     return dc
@@ -639,6 +646,17 @@ def corr_unpool_bwd_(dlevels, B, H, W):
     L.check(_lib().fsraft_corr_unpool_bwd(pp, len(dlevels), B, H, W, L.stream()), "corr_unpool_bwd")
 
 
+def corr_unpool_same_bwd_(dlevels, rows, h, w):
+    """In place: dlevels[0] [rows, 1, h, w] += the transposed 'SAME' poolings of dlevels[1 ..] (ceil sizes), the backward of
+    corr_pool_pyramid(..., same=True)."""
+    L.require_cuda_f32(*dlevels)
+    if [tuple(g.shape[-2:]) for g in dlevels] != same_sizes(h, w, len(dlevels)) or any(g.numel() != rows * g.shape[-2] * g.shape[-1] or
+                                                                                      not g.is_contiguous() for g in dlevels):
+        raise ValueError(f"corr_unpool_same_bwd_ takes contiguous ceil-sized levels of {rows} rows of {h}x{w}")
+    pp, keep = L.ptr_array(dlevels)
+    L.check(_lib().fsraft_corr_unpool_same_bwd(pp, len(dlevels), rows, h, w, L.stream()), "corr_unpool_same_bwd")
+
+
 def corr_lookup_fwd(levels, coords, radius, nhwc=False, same=False):
     """same=True: the pyramid has TensorFlow 'SAME' (ceil) level sizes."""
     L.require_cuda_f32(coords, *levels)
@@ -659,7 +677,8 @@ def corr_lookup_fwd(levels, coords, radius, nhwc=False, same=False):
     return out
 
 
-def corr_lookup_bwd_(dlevels, coords, dout, radius, nhwc=False):
+def corr_lookup_bwd_(dlevels, coords, dout, radius, nhwc=False, same=False):
+    """same=True: the level gradients have TensorFlow 'SAME' (ceil) sizes (fsraft_corr_lookup_bwd_same)."""
     L.require_cuda_f32(coords, dout, *dlevels)
     B, _, H, W = coords.shape
     bs, cs, ps = _planar2_strides(coords)
@@ -667,8 +686,8 @@ def corr_lookup_bwd_(dlevels, coords, dout, radius, nhwc=False):
     pp, keep = L.ptr_array(dlevels)
     t = TIMER
     e0 = t.begin() if t else None
-    L.check(_lib().fsraft_corr_lookup_bwd(pp, len(dlevels), L.ptr(coords), bs, cs, ps, L.ptr(dout), int(nhwc), B, H, W,
-                                          radius, L.stream()), "corr_lookup_bwd")
+    fn = _lib().fsraft_corr_lookup_bwd_same if same else _lib().fsraft_corr_lookup_bwd
+    L.check(fn(pp, len(dlevels), L.ptr(coords), bs, cs, ps, L.ptr(dout), int(nhwc), B, H, W, radius, L.stream()), "corr_lookup_bwd")
     if t:   # read dout, read-modify-write the window taps
         nl = len(dlevels)
         t.end("corr_lookup_bwd", e0, 0.0,

@@ -14,6 +14,9 @@ PyTorch-shaped API.  Pooling: the fused build pools with PyTorch's floor halving
 not 27 / 13 / 6).  When a pooled dimension is odd, calc_all_field and build_pyramid therefore build the pyramid with
 fsraft_corr_pool_pyramid_same and CorrBlock looks it up with fsraft_corr_lookup_fwd_same.  No TF oracle exists in this
 environment: the SAME path is tested against a restatement of TF's documented semantics (parity unpinned).
+Its backward is opt-in: with raft_tf.same_grad() on, the three calls are differentiable on 'SAME' pyramids too (the exact
+transpose of the forward above: fsraft_corr_unpool_same_bwd, fsraft_corr_lookup_bwd_same, fsraft_corr_lookup_dcoords_same);
+with it off, the default, such a call that wants a gradient raises.
 """
 from .api import (BasicUpdateBlock, CorrBlock, UpsampleConvexWithMask, build_pyramid, calc_all_field,  # noqa: F401
-                  transpose_volume)
+                  same_grad, transpose_volume)

@@ -54,6 +54,21 @@ int fsraft_corr_lookup_fwd_same(float* const* levels, int num_levels, const floa
                                 int64_t coords_cs, int64_t coords_ps, float* out, int nhwc_out, int B, int H, int W,
                                 int radius, hipStream_t stream);
 int fsraft_corr_unpool_bwd(float* const* dlevels, int num_levels, int B, int H, int W, hipStream_t stream);
+/* The backward of the 'SAME' pyramid and of the lookup over it, so that both are differentiable:
+ *   fsraft_corr_unpool_same_bwd      dlevels[0] += sum over l >= 1 of (the 'SAME' pooling of level l)^T dlevels[l], in place; sizes
+ *                                    and padding as fsraft_corr_pool_pyramid_same, num_levels 1..8, any rows >= 1; a level-0 cell
+ *                                    lies in one window per level and receives that window's gradient over its in-range count.
+ *                                    Levels >= 1 are only read; a gather without atomics (two calls give the same bits).
+ *   fsraft_corr_lookup_bwd_same      fsraft_corr_lookup_bwd onto level gradients of the ceil sizes (4 levels)
+ *   fsraft_corr_lookup_dcoords_same  fsraft_corr_lookup_dcoords on levels of the ceil sizes (num_levels 1..4)
+ * Bad arguments: FSRAFT_ERR_ARG and nothing is written. */
+int fsraft_corr_unpool_same_bwd(float* const* dlevels, int num_levels, int64_t rows, int H2, int W2, hipStream_t stream);
+int fsraft_corr_lookup_bwd_same(float* const* dlevels, int num_levels, const float* coords, int64_t coords_bs,
+                                int64_t coords_cs, int64_t coords_ps, const float* dout, int nhwc_in, int B, int H, int W,
+                                int radius, hipStream_t stream);
+int fsraft_corr_lookup_dcoords_same(float* const* levels, int num_levels, const float* coords, int64_t coords_bs, int64_t coords_cs,
+                                    int64_t coords_ps, const float* dout, int nhwc_in, float* dcoords, int64_t dbs, int64_t dcs,
+                                    int64_t dps, int B, int H, int W, int radius, hipStream_t stream);
 
 /* ---- the same volume in the tiled-row layout (what CorrBlock runs on) ------------------------------------------------
  * Every query i = (b, y, x) owns ONE row of P floats: its pyramid levels back to back, each level cut into 4x4-cell

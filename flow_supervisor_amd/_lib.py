@@ -130,6 +130,8 @@ SIGNATURES = {
     "fsraft_set_norm_blocks": [c_int],
     "fsraft_get_tuning": [c_int],
     "fsraft_conv_last_route": [c_int],
+    "fsraft_set_wgrad_wide": [c_int],
+    "fsraft_conv_wgrad_last_tile": [],
     "fsraft_space_to_depth2": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],
     "fsraft_forward_interpolate": [c_void_p, c_void_p, c_int, c_int, _S],
     "fsraft_flow_metrics_scratch_bytes": [c_int, c_int, c_int],

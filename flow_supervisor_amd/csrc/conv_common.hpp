@@ -25,6 +25,12 @@ struct ConvKnobs {
   int conv_uniform = 1;   // uniform-pitch k-tile table when the sources allow it (key 12)
   int conv_w8 = 1;        // 512-thread 128x128 tiles for wide layers (key 13); conv_w8_min: minimum workgroup count (key 14)
   int conv_w8_min = 64;      // (measured faster than 64x128 four-wave tiles on every update-block shape, N = 64 .. 576)
+  // Keys 2 / 11 size the pixel split of the 128x128 tile.  The wide tiles (256x256, 128x256; fsraft_set_wgrad_wide, no key) take
+  // at most that many splits, at most 512 workgroups and whole rounds of 256 (one workgroup per CU), and run by default where that
+  // grid has >= 192 workgroups of >= 16 k-tiles.  Measured, same process, hipGraph, us per launch, 128 tile -> wide (profiles/wgrad_wide_tiles.txt):
+  //   1x5 / 5x1 128+128->256 x12  719 -> 617 / 747 -> 641     1x5 / 5x1 128+128->128 x12  382 -> 361 / 397 -> 375
+  //   2x2 256->96  232 -> 198 (8x110x256), 127 -> 105 (4x110x256)     2x2 384->128  111 -> 95 (8x55x128), 66 -> 63 (4x55x128)
+  //   lost, grid of 52-104 workgroups: 1x1 256->576  491 -> 748, 1x1 324->256  323 -> 491, single five-tap 67 -> 93, 48 -> 66
   int wgrad_w8 = 0;       // 512-thread workgroups in the multi-segment weight gradient (key 15); measured slower (7.96 vs 7.32 ms/step): its grid is large already
   int wgrad_pack = 1;          // few-channel single-source layers on conv_wgrad_pack_kernel (key 16)
   int wgrad_blocks_pack = 1024;   // its workgroup target (key 17)
@@ -121,6 +127,10 @@ using SWCfg128 = SplitTnCfg<128, 128, 2, 2, 2>;
 using SWCfg128S = SplitTnCfg<128, 128, 2, 2, 1>;
 using SWCfg128W8 = SplitTnCfg<128, 128, 2, 4, 1, 512>;   // eight waves per workgroup (multi-segment launches)
 using SWCfgPack = SplitTnCfg<64, 192, 2, 2, 1>;
+// wide per-tap tiles (fsraft_set_wgrad_wide): eight waves, two LDS images, one workgroup per CU.  A 256-column x tile is two
+// 128-column groups of the packed-K layout (two taps or two sources), each loaded by one half of the workgroup.
+using SWCfgW256 = SplitTnCfg<256, 256, 2, 4, 2, 512>;      // 64 KB staged per k-tile for four times the MFMAs of the 128x128 tile's 32 KB
+using SWCfgW128 = SplitTnCfg<128, 256, 2, 4, 2, 512>;      // Cout <= 128 (the q layers): 0.75 of the bytes per MFMA
 using Cfg128 = GemmCfg<128, 128, 32, 2, 2, 2, 2>;
 using Cfg64 = GemmCfg<128, 64, 32, 4, 1, 2, 2>;
 using CfgM64 = GemmCfg<64, 128, 32, 1, 4, 2, 2>;     // half-height tile: doubles the workgroup count for narrow N

@@ -35,6 +35,17 @@ template <class L, class = void>
 struct has_fetch_tile : std::false_type {};
 template <class L>
 struct has_fetch_tile<L, std::void_t<decltype(&L::fetch_tile)>> : std::true_type {};
+// Loaders whose chunk c does not sit at tile element tid + NT * c say where it does with elem(c) (the 256-column x tile of the
+// weight gradient: each half of the workgroup loads its own 128-column half).
+template <class L, class = void>
+struct has_elem : std::false_type {};
+template <class L>
+struct has_elem<L, std::void_t<decltype(&L::elem)>> : std::true_type {};
+template <int NT, class L>
+__device__ __forceinline__ int chunk_elem(const L& l, int c) {
+  if constexpr (has_elem<L>::value) return l.elem(c);
+  else return threadIdx.x + NT * c;
+}
 template <class L, int N>
 __device__ __forceinline__ void fetch_all(const L& l, int kt, float (&r)[N]) {
   if constexpr (has_fetch_tile<L>::value) {
@@ -288,9 +299,9 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* p, int pitch) {
 }
 
 // COLSUM: additionally accumulate, per thread, the column sums of the A operand (its 4 columns are the same
-// for every chunk: (tid + 256 c) % (BM/4) == tid % (BM/4)) -- the bias gradient falls out of the weight
+// for every chunk: (tid + NT c) % (BM/4) == tid % (BM/4)) -- the bias gradient falls out of the weight
 // gradient's own loads.
-template <class Cfg, class LA, class LB, bool COLSUM = false>
+template <class Cfg, class LA, class LB, bool COLSUM = false, bool PIPE = false>
 __device__ __forceinline__ void split_mainloop_tn(char* __restrict__ lds, int KT, const LA& la, const LB& lb,
                                                   f32x16 (&acc)[Cfg::TM][Cfg::TN], float* colsum = nullptr) {
   static_assert(LA::NCH == Cfg::NCH_A && LB::NCH == Cfg::NCH_B, "loader tile shape must match the config");
@@ -310,20 +321,9 @@ __device__ __forceinline__ void split_mainloop_tn(char* __restrict__ lds, int KT
     }
 #pragma unroll
     for (int c = 0; c < LB::NCH; ++c)
-      stage_convert_kmajor<Cfg::BN, Cfg::PB, Cfg::B_PLANE>(dst + 2 * Cfg::A_PLANE, threadIdx.x + Cfg::NT * c, rb + 4 * c);
+      stage_convert_kmajor<Cfg::BN, Cfg::PB, Cfg::B_PLANE>(dst + 2 * Cfg::A_PLANE, chunk_elem<Cfg::NT>(lb, c), rb + 4 * c);
   };
-  if (KT > 0) {
-    fetch_all(la, 0, ra);
-    fetch_all(lb, 0, rb);
-    stage(lds, true);
-  }
-  __syncthreads();
-  for (int kt = 0; kt < KT; ++kt) {
-    char* cur = lds + (Cfg::NBUF == 2 ? (kt & 1) * Cfg::STAGE : 0);
-    char* nxt = lds + (Cfg::NBUF == 2 ? ((kt + 1) & 1) * Cfg::STAGE : 0);
-    const int ktn = (kt + 1 < KT) ? kt + 1 : kt;
-    fetch_all(la, ktn, ra);
-    fetch_all(lb, ktn, rb);
+  auto compute = [&](const char* cur) {
     // this lane's address inside a plane: row (8*lh + q) of the k-step, columns base + 16*gb + 4*p4
     const char* As = cur + (8 * lh + q) * Cfg::PA + (wm * (Cfg::TM * 32) + 16 * gb + 4 * p4) * 2;
     const char* Bs = cur + 2 * Cfg::A_PLANE + (8 * lh + q) * Cfg::PB + (wn * (Cfg::TN * 32) + 16 * gb + 4 * p4) * 2;
@@ -349,6 +349,58 @@ __device__ __forceinline__ void split_mainloop_tn(char* __restrict__ lds, int KT
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
         }
     }
+  };
+  if (KT > 0) {
+    fetch_all(la, 0, ra);
+    fetch_all(lb, 0, rb);
+    stage(lds, true);
+  }
+  if constexpr (PIPE) {
+    // Loads one k-tile further ahead: the registers filled while tile kt is multiplied are staged at the top of iteration kt + 1,
+    // so a load has a whole k-tile of MFMAs to land (in the loop below the compiler sinks the loads to their use, just before
+    // the staging code, and the wave then waits out the full memory latency once per k-tile).
+    static_assert(Cfg::NBUF == 2, "staging tile kt + 1 while tile kt is read needs two LDS images");
+    if (KT > 1) {
+      fetch_all(la, 1, ra);
+      fetch_all(lb, 1, rb);
+    }
+    __syncthreads();
+    auto advance = [&](int kt) {
+      if (kt + 1 < KT) {
+        stage(lds + ((kt + 1) & 1) * Cfg::STAGE, true);
+        const int k2 = kt + 2 < KT ? kt + 2 : KT - 1;      // (past the end: a harmless re-read that is never staged)
+        fetch_all(la, k2, ra);
+        fetch_all(lb, k2, rb);
+      }
+    };
+    // Between two barriers a wave stages tile kt + 1 into the image nobody reads and multiplies tile kt out of the other, in
+    // either order.  The first half of the waves stages first, the second half multiplies first: waves w and w + NT/128 share a
+    // SIMD, so its matrix pipe works for one of them while the other converts, writes LDS and reads its fragments.
+    if (__builtin_amdgcn_readfirstlane(wave) < Cfg::NT / 128) {
+      for (int kt = 0; kt < KT; ++kt) {
+        advance(kt);
+        __builtin_amdgcn_sched_barrier(0);                  // keep the loads above the MFMAs
+        compute(lds + (kt & 1) * Cfg::STAGE);
+        __syncthreads();
+      }
+    } else {
+      for (int kt = 0; kt < KT; ++kt) {
+        compute(lds + (kt & 1) * Cfg::STAGE);
+        __builtin_amdgcn_sched_barrier(0);
+        advance(kt);
+        __syncthreads();
+      }
+    }
+    return;
+  }
+  __syncthreads();
+  for (int kt = 0; kt < KT; ++kt) {
+    char* cur = lds + (Cfg::NBUF == 2 ? (kt & 1) * Cfg::STAGE : 0);
+    char* nxt = lds + (Cfg::NBUF == 2 ? ((kt + 1) & 1) * Cfg::STAGE : 0);
+    const int ktn = (kt + 1 < KT) ? kt + 1 : kt;
+    fetch_all(la, ktn, ra);
+    fetch_all(lb, ktn, rb);
+    compute(cur);
     if (Cfg::NBUF == 1) __syncthreads();
     stage(nxt, kt + 1 < KT);        // the last iteration re-stages its own tile: do not count it twice
     __syncthreads();

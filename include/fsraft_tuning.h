@@ -67,6 +67,13 @@ int fsraft_get_tuning(int key);
  *   5 bf16x3 128x128 single LDS image, 6 few-channel pack kernel, 7 resident-block kernel (wgrad_patch.inc), 8 multi-segment
  *   launch, 9 multi-segment launch with eight-wave workgroups (key 15). */
 int fsraft_conv_last_route(int which);
+/* Wide tiles of the per-tap weight-gradient kernel (routes 5 and 8 keep their codes): 256x256 (Cout >= 256) and 128x256, whose
+ * 256-column x tile is two 128-column groups of the packed-K layout; an odd last group and Cout beyond the last full 256 stay on
+ * the 128x128 tile.  0 off, 1 by shape (default: the layer classes that won their A/B), 2 wherever the shape allows. */
+int fsraft_set_wgrad_wide(int mode);
+/* The tile of the calling thread's last weight-gradient launch as BM << 16 | BN (dY columns x packed-K columns; the wide tile when a
+ * layer ran as wide tiles plus a 128x128 remainder); 0: none / rejected call / the resident-block kernel (no fixed tile). */
+int fsraft_conv_wgrad_last_tile(void);
 int fsraft_set_build_split(int on);   /* volume build: 1 bf16x3 (default), 0 exact fp32 MFMA */
 int fsraft_set_build_kernel(int which); /* record build: bits 8..15 start-up stagger of odd workgroups (x 64 x 127 cycles), bits 16..18 store policy (0 auto, 1 plain, 2 sc1, 3 nt) */
 /* cache policy of the tiled lookup's window loads: -1 auto (nt for volumes beyond the Infinity Cache; default), 0 plain, 2 nt,

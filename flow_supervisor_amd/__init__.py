@@ -8,5 +8,7 @@ Layout mirrors the reference's PyTorch tree so it drops in:
     flow_supervisor_amd.alt_cuda_corr  forward / backward                 (pytorch/alt_cuda_corr)
     flow_supervisor_amd.evaluate       validate_chairs / _sintel / _kitti / _kitti2012, create_*_submission, FlowMetrics
                                                                           (pytorch/evaluate.py)
+    flow_supervisor_amd.unsup_loss     UnsupervisedLoss, census_loss, smoothness_loss, range_map, occlusion_mask
+                                                                          (raft/unsup_loss.py, raft/smurf_models/smurf_utils.py)
 The compute lives in csrc/*.hip behind the C ABI of include/fsraft.h (libfsraft.so).
 """

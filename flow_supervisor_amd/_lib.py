@@ -137,6 +137,18 @@ SIGNATURES = {
     "fsraft_flow_metrics_scratch_bytes": [c_int, c_int, c_int],
     "fsraft_flow_metrics": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_range_map_scratch_bytes": [c_int, c_int, c_int],
+    "fsraft_range_map": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_census_scratch_bytes": [c_int, c_int, c_int],
+    "fsraft_census_fwd": [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP,
+                          c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                          c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_census_bwd": [c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP,
+                          c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                          c_void_p, _S],
+    "fsraft_smoothness_scratch_bytes": [c_int, c_int, c_int],
+    "fsraft_smoothness": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP, c_void_p, c_int64, c_int64, c_int64,
+                          c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int64, _S],
     "fsraft_inorm_relu_cl_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _S],
     "fsraft_inorm_relu_cl_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, _S],

@@ -1527,3 +1527,107 @@ def flow_metrics(pred, gt, valid, sample_stats, acc=None, scratch=None):
                                        L.ptr(sample_stats), L.ptr(acc), L.ptr(scratch), scratch.numel() * scratch.element_size(),
                                        L.stream()), "flow_metrics")
     return sample_stats
+
+
+# ------------------------------------------------------------------ unsupervised (SMURF) loss
+def _scratch_f64(fn, what, B, H, W, device):
+    n = fn(B, H, W)
+    if n == 1:
+        raise RuntimeError(f"libfsraft: {what}_scratch_bytes({B}, {H}, {W}) failed with status 1 (bad argument)")
+    return torch.empty(n // 8, device=device, dtype=torch.float64)
+
+
+def _unit_x(what, *tensors):
+    if any(t is not None and t.shape[-1] > 1 and t.stride(-1) != 1 for t in tensors):
+        raise RuntimeError(f"{what}: every view needs a unit x stride")
+
+
+def crop_offsets(crop_yx, B):
+    """The [B,2] (y, x) window offsets as the host int array the entry points take (None: no offsets).  They are read on the host
+    before any launch, so a device tensor is refused: reading it would synchronise."""
+    if crop_yx is None:
+        return None
+    if isinstance(crop_yx, torch.Tensor):
+        if crop_yx.is_cuda:
+            raise RuntimeError("crop_yx is read on the host (it is checked before any launch): pass a CPU tensor or a list")
+        crop_yx = crop_yx.tolist()
+    flat = [int(v) for row in crop_yx for v in row]
+    if len(flat) != 2 * B:
+        raise RuntimeError(f"crop_yx needs {B} (y, x) pairs, got {len(flat) // 2}")
+    return L.int_array(flat)
+
+
+def range_map(flow, clip=False):
+    """fsraft_range_map: flow [B,2,H,W] -> [B,H,W], the bilinear landing weights of every q + flow(q) (clip: min(R, 1))."""
+    L.require_cuda_f32(flow)
+    B, C, H, W = flow.shape
+    if C != 2:
+        raise RuntimeError(f"range_map: flow {tuple(flow.shape)}")
+    _unit_x("range_map", flow)
+    out = torch.empty(B, H, W, device=flow.device, dtype=torch.float32)
+    scratch = _scratch_f64(_lib().fsraft_range_map_scratch_bytes, "range_map", B, H, W, flow.device)
+    L.check(_lib().fsraft_range_map(L.ptr(flow), *flow.stride()[:3], B, H, W, int(bool(clip)), L.ptr(out), L.ptr(scratch),
+                                    scratch.numel() * 8, L.stream()), "range_map")
+    return out
+
+
+def _census_views(img1, img1_frame, img2, flow, crop):
+    B, C, H, W = flow.shape
+    Hf, Wf = img2.shape[-2:]
+    ok = C == 2 and img2.shape[:2] == (B, 3) and img1.shape == ((B, 3, Hf, Wf) if img1_frame else (B, 3, H, W))
+    if not ok:
+        raise RuntimeError(f"census: image1 {tuple(img1.shape)}, image2 {tuple(img2.shape)}, flow {tuple(flow.shape)}")
+    _unit_x("census", img1, img2, flow)
+    return (L.ptr(img1), *img1.stride()[:3], int(img1_frame), L.ptr(img2), *img2.stride()[:3], Hf, Wf, crop,
+            L.ptr(flow), *flow.stride()[:3])
+
+
+def census_fwd(img1, img2, flow, mask, crop=None, img1_frame=False):
+    """fsraft_census_fwd.  img2 [B,3,Hf,Wf] is the frame the warp samples, img1 the H x W image i (or, img1_frame, its frame);
+    flow [B,2,H,W]; mask [B,H,W] or None; crop: crop_offsets(...) or None.  Returns (out fp64 [2] = loss, denominator; grayB;
+    hplane), the last two [B,H,W] for census_bwd."""
+    L.require_cuda_f32(img1, img2, flow, mask)
+    B, _, H, W = flow.shape
+    if mask is not None and mask.shape != (B, H, W):
+        raise RuntimeError(f"census: mask {tuple(mask.shape)} for flow {tuple(flow.shape)}")
+    _unit_x("census", mask)
+    views = _census_views(img1, img1_frame, img2, flow, crop)
+    grayB = torch.empty(B, H, W, device=flow.device, dtype=torch.float32)
+    hplane = torch.empty_like(grayB)
+    out = torch.empty(2, device=flow.device, dtype=torch.float64)
+    scratch = _scratch_f64(_lib().fsraft_census_scratch_bytes, "census", B, H, W, flow.device)
+    ms = (mask.stride(0), mask.stride(1)) if mask is not None else (0, 0)
+    L.check(_lib().fsraft_census_fwd(*views, L.ptr(mask), *ms, B, H, W, L.ptr(grayB), L.ptr(hplane), L.ptr(out), L.ptr(scratch),
+                                     scratch.numel() * 8, L.stream()), "census_fwd")
+    return out, grayB, hplane
+
+
+def census_bwd(img1, img2, flow, grayB, hplane, up, den, crop=None, img1_frame=False):
+    """fsraft_census_bwd: d loss / d flow [B,2,H,W]; up: fp32 device scalar (the upstream gradient), den: fp64 device scalar
+    (out[1:] of census_fwd)."""
+    L.require_cuda_f32(img1, img2, flow, grayB, hplane, up)
+    B, _, H, W = flow.shape
+    views = _census_views(img1, img1_frame, img2, flow, crop)
+    if not (grayB.is_contiguous() and hplane.is_contiguous() and grayB.shape == hplane.shape == (B, H, W)) or den.dtype != torch.float64:
+        raise RuntimeError("census_bwd: grayB / hplane must be the contiguous planes and den the fp64 scalar of census_fwd")
+    dflow = torch.empty(B, 2, H, W, device=flow.device, dtype=torch.float32)
+    L.check(_lib().fsraft_census_bwd(*views, L.ptr(grayB), L.ptr(hplane), L.ptr(up), L.ptr(den), B, H, W, L.ptr(dflow), L.stream()),
+            "census_bwd")
+    return dflow
+
+
+def smoothness(img, flow, order=1, edge_constant=150.0, gaussian=False, crop=None):
+    """fsraft_smoothness: img [B,3,Hf,Wf] (the H x W window at `crop`, or the image itself), flow [B,2,H,W].  Returns (out fp64 [1],
+    dflow [B,2,H,W] = d out / d flow)."""
+    L.require_cuda_f32(img, flow)
+    B, C, H, W = flow.shape
+    if C != 2 or img.shape[:2] != (B, 3):
+        raise RuntimeError(f"smoothness: image {tuple(img.shape)}, flow {tuple(flow.shape)}")
+    _unit_x("smoothness", img, flow)
+    dflow = torch.empty(B, 2, H, W, device=flow.device, dtype=torch.float32)
+    out = torch.empty(1, device=flow.device, dtype=torch.float64)
+    scratch = _scratch_f64(_lib().fsraft_smoothness_scratch_bytes, "smoothness", B, H, W, flow.device)
+    L.check(_lib().fsraft_smoothness(L.ptr(img), *img.stride()[:3], img.shape[2], img.shape[3], crop, L.ptr(flow), *flow.stride()[:3],
+                                     B, H, W, int(order), float(edge_constant), int(bool(gaussian)), L.ptr(dflow), L.ptr(out),
+                                     L.ptr(scratch), scratch.numel() * 8, L.stream()), "smoothness")
+    return out, dflow

@@ -449,6 +449,56 @@ int fsraft_flow_metrics(const float* pred, int64_t pred_bs, int64_t pred_cs, int
                         const float* valid, int64_t valid_bs, int64_t valid_rs, int B, int H, int W,
                         double* sample_stats, double* acc, void* scratch, int64_t scratch_bytes, hipStream_t stream);
 
+/* ---- unsupervised (SMURF) loss (a step next to the path: raft/unsup_loss.py UnsupervisedLoss over
+ * raft/smurf_models/smurf_utils.py: compute_range_map, census_loss, first/second_order_smoothness_loss) -------------------
+ * PyTorch layout: images [B][3][.][.] in [0,1], flows [B][2][H][W] with channel 0 = x (the reference's tf.reverse to
+ * (row, col) is absorbed).  Every view comes with strides in elements and a unit x stride.  An image argument is a frame of
+ * Hf x Wf of which sample b uses the H x W window at (crop_yx[2b], crop_yx[2b+1]) = (y, x); crop_yx is a HOST array of
+ * 2 * B ints (NULL: all zero), read during the call and passed to the kernels by value, so a captured call keeps its
+ * offsets.  Per-pixel arithmetic is fp32, sums are fp64 in workgroup order through `scratch` (8-byte aligned, at least the
+ * _scratch_bytes companion's size, nothing to initialise); results are bit-identical from run to run, and the per-pixel
+ * outputs of sample b do not depend on the rest of the batch.  No allocation, no synchronisation.  FSRAFT_ERR_ARG, before any
+ * HIP call, for a null pointer, B, H or W below 1 (census: H or W below 7; smoothness: H or W <= order), H * W or Hf * Wf beyond
+ * 2^31 - 1, a window outside the frame, a misaligned fp64 pointer or too little scratch.
+ *
+ * fsraft_range_map: out [B][H][W] = R[p] = the bilinear weights of every q + flow(q) that land on p (taps outside the image
+ * and zero weights are skipped), summed exactly in 64-bit fixed point (units of 2^-32; integer atomics commute) and rounded
+ * to fp32 once; clip != 0 gives min(R, 1), the 'wang' mask of the opposite direction (occlusions_are_zeros).
+ *
+ * fsraft_census_fwd: img2 is a frame; img1 is one too when img1_frame != 0 (the same offsets), else the H x W image i itself.
+ * Iw[p] = bilinear(img2, p + crop + flow(p)) with zero taps outside the frame, valid[p] = that point
+ * inside [0, Wf-1] x [0, Hf-1], M = mask * valid (mask [B][H][W], NULL: 1) and zero on a 3-pixel border;
+ * gray = 255 * (0.2989 R + 0.5870 G + 0.1140 B), c_k = d / sqrt(0.81 + d^2) over the 7 x 7 patch, ham = sum_k u^2 / (0.1 + u^2)
+ * with u = cA_k - cB_k, l = (ham + 0.01)^0.4.  out[0] = sum l * M / out[1], out[1] = sum M + 1e-6 * B * H * W.  Saved for the
+ * backward, [B][H][W] each: grayB = gray(Iw), hplane = M * 0.4 * (ham + 0.01)^-0.6.
+ * fsraft_census_bwd: dflow [B][2][H][W] (every element written) = up[0] / den[0] * dL/dgray(Iw) * d gray(Iw) / d(x, y), the
+ * resampler's coordinate gradient with the zero-tap rule; up (fp32) and den (fp64, out + 1 of the forward) are device scalars.
+ * A pixel none of whose 7 x 7 neighbours has M != 0 gets +0.0.
+ *
+ * fsraft_smoothness: order 1: (mean(w_y * r(D_y f)) + mean(w_x * r(D_x f))) / 2 with forward differences, r(x) =
+ * sqrt(x^2 + 1e-6) and w = exp(-mean_c |k * D I|) (gaussian != 0: exp(-mean_c (k * D I)^2)), k = edge_constant; order 2:
+ * second differences of the flow and stride-2 differences of the image.  out[0] = the value, dflow [B][2][H][W] = its
+ * gradient, both from one pass. */
+int fsraft_range_map_scratch_bytes(int B, int H, int W);
+int fsraft_range_map(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs, int B, int H, int W, int clip,
+                     float* out, void* scratch, int64_t scratch_bytes, hipStream_t stream);
+int fsraft_census_scratch_bytes(int B, int H, int W);
+int fsraft_census_fwd(const float* img1, int64_t img1_bs, int64_t img1_cs, int64_t img1_rs, int img1_frame,
+                      const float* img2, int64_t img2_bs, int64_t img2_cs, int64_t img2_rs, int Hf, int Wf,
+                      const int* crop_yx, const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs,
+                      const float* mask, int64_t mask_bs, int64_t mask_rs, int B, int H, int W,
+                      float* grayB, float* hplane, double* out, void* scratch, int64_t scratch_bytes, hipStream_t stream);
+int fsraft_census_bwd(const float* img1, int64_t img1_bs, int64_t img1_cs, int64_t img1_rs, int img1_frame,
+                      const float* img2, int64_t img2_bs, int64_t img2_cs, int64_t img2_rs, int Hf, int Wf,
+                      const int* crop_yx, const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs,
+                      const float* grayB, const float* hplane, const float* up, const double* den, int B, int H, int W,
+                      float* dflow, hipStream_t stream);
+int fsraft_smoothness_scratch_bytes(int B, int H, int W);
+int fsraft_smoothness(const float* img, int64_t img_bs, int64_t img_cs, int64_t img_rs, int Hf, int Wf, const int* crop_yx,
+                      const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs, int B, int H, int W, int order,
+                      float edge_constant, int gaussian, float* dflow, double* out, void* scratch, int64_t scratch_bytes,
+                      hipStream_t stream);
+
 /* Channels-last ([B][HW][C], C % 4 == 0, C <= 256) variants, for the encoder stages whose convolutions run on
  * fsraft_conv_forward.  sums/sumsq/s1/s2 and dsum_g/dsum_gx: [B * 8][C] partial rows (workgroups spread their atomics over
  * eight rows per sample: thousands of adds on the same C addresses serialise in L2 otherwise; dsum_*: the per-channel sums

@@ -10,5 +10,7 @@ Layout mirrors the reference's PyTorch tree so it drops in:
                                                                           (pytorch/evaluate.py)
     flow_supervisor_amd.unsup_loss     UnsupervisedLoss, census_loss, smoothness_loss, range_map, occlusion_mask
                                                                           (raft/unsup_loss.py, raft/smurf_models/smurf_utils.py)
+    flow_supervisor_amd.selfsup_loss   SmurfLoss, self_supervision_loss, brox_occlusion_mask, fb_consistency_mask
+                                                                          (the same two files: selfsup and 'brox')
 The compute lives in csrc/*.hip behind the C ABI of include/fsraft.h (libfsraft.so).
 """

@@ -149,6 +149,12 @@ SIGNATURES = {
     "fsraft_smoothness_scratch_bytes": [c_int, c_int, c_int],
     "fsraft_smoothness": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP, c_void_p, c_int64, c_int64, c_int64,
                           c_int, c_int, c_int, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_fb_mask": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP,
+                       c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, _S],
+    "fsraft_selfsup_scratch_bytes": [c_int, c_int, c_int],
+    "fsraft_selfsup": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP, c_void_p, c_int64, c_int64,
+                       c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                       c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, _S],
     "fsraft_inorm_relu_cl_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _S],
     "fsraft_inorm_relu_cl_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, _S],

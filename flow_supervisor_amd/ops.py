@@ -1631,3 +1631,53 @@ def smoothness(img, flow, order=1, edge_constant=150.0, gaussian=False, crop=Non
                                      B, H, W, int(order), float(edge_constant), int(bool(gaussian)), L.ptr(dflow), L.ptr(out),
                                      L.ptr(scratch), scratch.numel() * 8, L.stream()), "smoothness")
     return out, dflow
+
+
+FB_MODES = {"gaussian": 0, "ddflow": 1, "brox": 2, "none": 3}      # FSRAFT_FB_* of include/fsraft.h
+
+
+def _frame_of(what, frame, B, H, W):
+    if frame.dim() != 4 or frame.shape[:2] != (B, 2) or frame.shape[2] < H or frame.shape[3] < W:
+        raise RuntimeError(f"{what}: a [{B},2,>={H},>={W}] flow, got {tuple(frame.shape)}")
+
+
+def fb_mask(flow, flow_back, mode, norm=1.0, complement=False, hw=None, crop=None):
+    """fsraft_fb_mask: flow, flow_back [B,2,Hf,Wf] -> [B,H,W] on the (H, W) = hw window at `crop` (crop_offsets(...); hw None:
+    the whole frame).  mode 'gaussian' (exp(-sq / norm)) or 'ddflow': c * valid, complement: 1 - c * valid; 'brox': visible."""
+    L.require_cuda_f32(flow, flow_back)
+    if mode not in ("gaussian", "ddflow", "brox"):
+        raise RuntimeError(f"fb_mask: mode {mode!r}")
+    B, C, Hf, Wf = flow.shape
+    H, W = (Hf, Wf) if hw is None else hw
+    if C != 2 or flow_back.shape != flow.shape:
+        raise RuntimeError(f"fb_mask: flow {tuple(flow.shape)}, flow_back {tuple(flow_back.shape)}")
+    _frame_of("fb_mask", flow, B, H, W)
+    _unit_x("fb_mask", flow, flow_back)
+    out = torch.empty(B, H, W, device=flow.device, dtype=torch.float32)
+    L.check(_lib().fsraft_fb_mask(L.ptr(flow), *flow.stride()[:3], L.ptr(flow_back), *flow_back.stride()[:3], Hf, Wf, crop, B, H, W,
+                                  FB_MODES[mode], int(bool(complement)), float(norm), L.ptr(out), L.stream()), "fb_mask")
+    return out
+
+
+def selfsup(teacher, teacher_mask, student, student_back, mode, norm=1.0, crop=None):
+    """fsraft_selfsup: teacher [B,2,Hf,Wf] (its window at `crop`), teacher_mask [B,H,W] or None, student and student_back
+    [B,2,H,W]; mode 'gaussian', 'ddflow' or 'none'.  Returns (out fp64 [1] = the masked robust-L1 mean, dflow [B,2,H,W] =
+    d out / d student)."""
+    L.require_cuda_f32(teacher, teacher_mask, student, student_back)
+    if mode not in ("gaussian", "ddflow", "none"):
+        raise RuntimeError(f"selfsup: mode {mode!r}")
+    B, C, H, W = student.shape
+    if C != 2 or student_back.shape != student.shape or (teacher_mask is not None and teacher_mask.shape != (B, H, W)):
+        raise RuntimeError(f"selfsup: student {tuple(student.shape)}, student_back {tuple(student_back.shape)}, "
+                           f"teacher_mask {None if teacher_mask is None else tuple(teacher_mask.shape)}")
+    _frame_of("selfsup: teacher", teacher, B, H, W)
+    _unit_x("selfsup", teacher, teacher_mask, student, student_back)
+    dflow = torch.empty(B, 2, H, W, device=student.device, dtype=torch.float32)
+    out = torch.empty(1, device=student.device, dtype=torch.float64)
+    scratch = _scratch_f64(_lib().fsraft_selfsup_scratch_bytes, "selfsup", B, H, W, student.device)
+    ms = (teacher_mask.stride(0), teacher_mask.stride(1)) if teacher_mask is not None else (0, 0)
+    L.check(_lib().fsraft_selfsup(L.ptr(teacher), *teacher.stride()[:3], teacher.shape[2], teacher.shape[3], crop, L.ptr(teacher_mask), *ms,
+                                  L.ptr(student), *student.stride()[:3], L.ptr(student_back), *student_back.stride()[:3], B, H, W,
+                                  FB_MODES[mode], float(norm), L.ptr(dflow), L.ptr(out), L.ptr(scratch), scratch.numel() * 8, L.stream()),
+            "selfsup")
+    return out, dflow

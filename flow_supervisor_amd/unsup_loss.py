@@ -13,7 +13,8 @@ first; that is absorbed).  Everything is differentiable with respect to the flow
 reference stops the gradient of the mask).  CUDA (ROCm) fp32 tensors only: there is no CPU implementation.
 
 Not implemented, and refused with NotImplementedError: selfsup > 0 (needs the teacher / student crop-and-resize machinery),
-occlusion 'brox' and mode 'unsup_final_update'.
+occlusion 'brox' and mode 'unsup_final_update'.  The first two are what selfsup_loss.SmurfLoss adds (the reference's transform
+turned out to be a plain crop); this module's behaviour is unchanged.
 """
 import torch
 
@@ -122,7 +123,7 @@ class UnsupervisedLoss:
     def __init__(self, census=1.0, smooth1=2.5, smooth2=0.0, selfsup=0.0, occlusion="wang", gamma=0.8, mode="unsup_per_update"):
         if selfsup > 0:
             raise NotImplementedError("selfsup > 0 needs the teacher / student crop-and-resize machinery, which is not implemented "
-                                      "(the reference's default is 0.3; pass 0)")
+                                      "here (the reference's default is 0.3; pass 0, or use selfsup_loss.SmurfLoss)")
         if occlusion == "brox":
             raise NotImplementedError("occlusion 'brox' (forward-backward consistency) is not implemented; use 'wang' or 'none'")
         if occlusion not in ("wang", "none"):

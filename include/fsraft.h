@@ -499,6 +499,48 @@ int fsraft_smoothness(const float* img, int64_t img_bs, int64_t img_cs, int64_t 
                       float edge_constant, int gaussian, float* dflow, double* out, void* scratch, int64_t scratch_bytes,
                       hipStream_t stream);
 
+/* ---- forward-backward consistency masks and the self-supervision term of the SMURF loss (smurf_utils.py
+ * compute_occlusions_brox :432-453, self_supervision_loss :735-829 with a plain crop as the transform) ---------------------
+ * Conventions of the section above: flows [B][2][.][.] with channel 0 = x, strides in elements with a unit x stride, frames
+ * of Hf x Wf with the H x W window of sample b at (crop_yx[2b], crop_yx[2b+1]) = (y, x) (HOST array, NULL: all zero; with
+ * Hf = H and Wf = W the views are the images themselves), fp32 per pixel with one rounding per operation, fp64 sums in
+ * workgroup order through `scratch`; bit-identical from run to run, capturable, no allocation, no synchronisation.
+ * For a pair (f, g) over an image of Hi x Wi, at pixel p: r = bilinear(g, p + f(p)) with zero taps outside the image,
+ * sq = |f + r|^2, ss = |f|^2 + |r|^2, valid = p + f(p) inside [0, Wi-1] x [0, Hi-1].  The consistency c is
+ * exp(-sq / norm) (FSRAFT_FB_GAUSSIAN; norm = sigma^2 * (h^2 + w^2), chosen by the caller) or [sq < 0.01 ss + 0.5]
+ * (FSRAFT_FB_DDFLOW).
+ * FSRAFT_ERR_ARG, before any HIP call, for a null pointer (teacher_mask excepted), B, H or W below 1, H * W or Hf * Wf beyond
+ * 2^31 - 1, a frame smaller than the window, a window outside the frame, an unknown mode (FSRAFT_FB_BROX is one for
+ * fsraft_selfsup, FSRAFT_FB_NONE for fsraft_fb_mask), complement other than 0 or 1, norm <= 0 (or NaN) in gaussian mode, a
+ * misaligned fp64 pointer or too little scratch.
+ *
+ * fsraft_fb_mask: flow and flow_back are frames and the image of the pair is the frame; out [B][H][W] (every element
+ * written) is evaluated on the window: c * valid (complement 0) or 1 - c * valid (complement 1; the gaussian's as
+ * -expm1(-sq / norm), which keeps its relative accuracy next to c = 1, here and in fsraft_selfsup) in the gaussian and ddflow
+ * modes; FSRAFT_FB_BROX gives visible = 1 - [sq > 0.01 ss + 0.5], without the valid factor (a warp outside the frame has
+ * r = 0) and whatever complement says.
+ *
+ * fsraft_selfsup: teacher is a frame [B][2][Hf][Wf] of which the window is read; teacher_mask [B][H][W] (NULL: ones) is what
+ * fsraft_fb_mask left for the teacher's pair, computed once and reused by every prediction; student and student_back are
+ * [B][2][H][W] and their image is the H x W window itself.  m = teacher_mask * (1 - c * valid) of the student's pair, formed
+ * in registers (FSRAFT_FB_NONE: m = teacher_mask); d = teacher - student, e = sqrt(d^2 + 1e-6) per channel.
+ * out[0] = sum m * (e_x + e_y) / (2 * B * H * W); dflow [B][2][H][W] (every element written) = d out[0] / d student =
+ * -m * d / e / (2 * H * W) / B, divided in that order, so that a sample alone gives, divided by B, the bits it gives in the
+ * batch; +0.0 where m == 0.  No gradient for the teacher, the mask or student_back. */
+#define FSRAFT_FB_GAUSSIAN 0
+#define FSRAFT_FB_DDFLOW 1
+#define FSRAFT_FB_BROX 2
+#define FSRAFT_FB_NONE 3
+int fsraft_fb_mask(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs,
+                   const float* flow_back, int64_t back_bs, int64_t back_cs, int64_t back_rs, int Hf, int Wf,
+                   const int* crop_yx, int B, int H, int W, int mode, int complement, float norm, float* out, hipStream_t stream);
+int fsraft_selfsup_scratch_bytes(int B, int H, int W);
+int fsraft_selfsup(const float* teacher, int64_t teacher_bs, int64_t teacher_cs, int64_t teacher_rs, int Hf, int Wf,
+                   const int* crop_yx, const float* teacher_mask, int64_t tmask_bs, int64_t tmask_rs,
+                   const float* student, int64_t student_bs, int64_t student_cs, int64_t student_rs,
+                   const float* student_back, int64_t sback_bs, int64_t sback_cs, int64_t sback_rs, int B, int H, int W,
+                   int mode, float norm, float* dflow, double* out, void* scratch, int64_t scratch_bytes, hipStream_t stream);
+
 /* Channels-last ([B][HW][C], C % 4 == 0, C <= 256) variants, for the encoder stages whose convolutions run on
  * fsraft_conv_forward.  sums/sumsq/s1/s2 and dsum_g/dsum_gx: [B * 8][C] partial rows (workgroups spread their atomics over
  * eight rows per sample: thousands of adds on the same C addresses serialise in L2 otherwise; dsum_*: the per-channel sums

@@ -12,5 +12,7 @@ Layout mirrors the reference's PyTorch tree so it drops in:
                                                                           (raft/unsup_loss.py, raft/smurf_models/smurf_utils.py)
     flow_supervisor_amd.selfsup_loss   SmurfLoss, self_supervision_loss, brox_occlusion_mask, fb_consistency_mask
                                                                           (the same two files: selfsup and 'brox')
+    flow_supervisor_amd.augment        UnsupAugmentor, apply, as_step_input, add_noise
+                                                                          (pytorch/raft_utils/augmentor.py:496-657)
 The compute lives in csrc/*.hip behind the C ABI of include/fsraft.h (libfsraft.so).
 """

@@ -50,6 +50,19 @@ class PackJob(Structure):
     ]
 
 
+class AugParams(Structure):
+    """Mirror of fsraft_aug_params (include/fsraft.h)."""
+    _fields_ = [
+        ("resize", c_int), ("th", c_int), ("tw", c_int),
+        ("scale_x", c_float), ("scale_y", c_float),
+        ("win_y", c_int), ("win_x", c_int), ("hflip", c_int), ("vflip", c_int), ("crop_y", c_int), ("crop_x", c_int),
+        ("asym", c_int),
+        ("brightness", c_float * 2), ("contrast", c_float * 2), ("saturation", c_float * 2), ("hue", c_float * 2),
+        ("nrect", c_int),
+        ("rect", (c_int * 4) * 2),
+    ]
+
+
 _PP = POINTER(c_void_p)
 _IP = POINTER(c_int)
 _S = c_void_p   # hipStream_t
@@ -155,6 +168,9 @@ SIGNATURES = {
     "fsraft_selfsup": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, _IP, c_void_p, c_int64, c_int64,
                        c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int,
                        c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_augment_scratch_bytes": [c_int, c_int, c_int, c_int, c_int],
+    "fsraft_augment": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(AugParams), c_int, c_int, c_int, c_int,
+                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _S],
     "fsraft_inorm_relu_cl_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _S],
     "fsraft_inorm_relu_cl_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, _S],

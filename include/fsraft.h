@@ -541,6 +541,56 @@ int fsraft_selfsup(const float* teacher, int64_t teacher_bs, int64_t teacher_cs,
                    const float* student_back, int64_t sback_bs, int64_t sback_cs, int64_t sback_rs, int B, int H, int W,
                    int mode, float norm, float* dflow, double* out, void* scratch, int64_t scratch_bytes, hipStream_t stream);
 
+/* ---- UnsupAugmentor applied to a batch (csrc/augment.hip; flow_supervisor_amd/augment.py draws the parameters) ----------
+ * pytorch/raft_utils/augmentor.py:496-657 (spatial_transform, color_transform, eraser_transform), ColorJitter :15-37 and the
+ * "* 255" of pytorch/train.py:251-258.  The reference's augmentor is TensorFlow on the host and does not run here: the formulas
+ * below are the definition (restated in float64 in tests/_augref.py).
+ *
+ * Sources are interleaved: image1 / image2 [B][Hs][Ws][3], uint8 in [0, 255] (FSRAFT_AUG_U8) or float in [0, 1]
+ * (FSRAFT_AUG_F32); flow [B][Hs][Ws][2]; valid [B][Hs][Ws] (NULL: ones).  params is a HOST array of B structs, read and checked
+ * during the call and passed to the kernels by value, so a captured call keeps its parameters.  Outputs are planar, contiguous
+ * fp32, every element written: frame1 / frame2 [B][3][Hf][Wf] in [0, 255] without photometric change, frame_flow [B][2][Hf][Wf],
+ * frame_valid [B][1][Hf][Wf], crop1 / crop2 [B][3][h][w] in [0, 255] after colour and eraser, crop_flow [B][2][h][w],
+ * crop_valid [B][1][h][w].
+ *
+ * Frame pixel (y, x) of sample b is pixel (vflip ? Hf-1-y : y) + win_y, (hflip ? Wf-1-x : x) + win_x of the source resized to
+ * th x tw (resize 0: the source itself, th = Hs, tw = Ws).  Images: TF2 tf.image.resize(BILINEAR), half-pixel centres, no
+ * antialias: src = (dst + 0.5) * (in / out) - 0.5, lo = max(floor(src), 0), hi = min(ceil(src), in - 1), weight src - floor(src),
+ * along x within the two rows, then along y; a float source is multiplied by 255 afterwards.  Flow and valid: NEAREST_NEIGHBOR,
+ * index min(floor((dst + 0.5) * (in / out)), in - 1); all of this index arithmetic in float32.  The flow is multiplied by
+ * (scale_x, scale_y), by (-1, 1) under hflip and by (1, -1) under vflip.  The crop is the h x w window of the frame at
+ * (crop_y, crop_x).
+ * Colour, per image i on x = frame / 255: x * brightness[i]; (x - mean) * contrast[i] + mean with the per-channel mean of the
+ * brightness-scaled crop (asym 0: over both crops); RGB -> HSV -> RGB with s = clip(s * saturation[i], 0, 1); again with
+ * h = frac(h + hue[i]); clip to [0, 1]; * 255.  HSV: v = max, c = max - min, s = c / v (0 when v <= 0), h the hexcone sector in
+ * [0, 1) (0 when c = 0); back: ((d - 1) * s + 1) * v with d = clip(|6h - 3| - 1), clip(2 - |6h - 2|), clip(2 - |6h - 4|) in [0, 1].
+ * Eraser: rect[r] = (x0, y0, dx, dy), r < nrect, of crop2 is overwritten with crop2's per-channel mean after the colour step
+ * and before any rectangle; an empty rectangle writes nothing.
+ *
+ * Sums are fp64 per workgroup in `scratch` (8-byte aligned, at least fsraft_augment_scratch_bytes, nothing to initialise) and
+ * added in workgroup order: no float atomics, bit-identical from run to run.  No allocation, no synchronisation; four launches
+ * per 16 samples (three when none of them has a rectangle).
+ * FSRAFT_ERR_ARG, before any HIP call, for a null (valid excepted) or misaligned pointer, an unknown dtype, a size below 1,
+ * Hs * Ws * 3, Hf * Wf * 3 or th * tw beyond 2^31 - 1, h > Hf or w > Wf, th < Hf or tw < Wf, resize 0 with (th, tw) != (Hs, Ws),
+ * a window outside the resized image, a crop outside the frame, a rectangle outside the crop, nrect outside 0..2, a flag
+ * other than 0 or 1, a non-finite factor, asym 0 with factors that differ between the two images, or too little scratch. */
+#define FSRAFT_AUG_U8 0
+#define FSRAFT_AUG_F32 1
+typedef struct fsraft_aug_params {
+  int resize, th, tw;
+  float scale_x, scale_y;
+  int win_y, win_x, hflip, vflip, crop_y, crop_x;
+  int asym;
+  float brightness[2], contrast[2], saturation[2], hue[2];
+  int nrect;
+  int rect[2][4];
+} fsraft_aug_params;
+int fsraft_augment_scratch_bytes(int B, int Hf, int Wf, int h, int w);
+int fsraft_augment(const void* image1, const void* image2, int dtype, const float* flow, const float* valid, int B, int Hs, int Ws,
+                   const fsraft_aug_params* params, int Hf, int Wf, int h, int w, float* frame1, float* frame2, float* frame_flow,
+                   float* frame_valid, float* crop1, float* crop2, float* crop_flow, float* crop_valid, void* scratch,
+                   int64_t scratch_bytes, hipStream_t stream);
+
 /* Channels-last ([B][HW][C], C % 4 == 0, C <= 256) variants, for the encoder stages whose convolutions run on
  * fsraft_conv_forward.  sums/sumsq/s1/s2 and dsum_g/dsum_gx: [B * 8][C] partial rows (workgroups spread their atomics over
  * eight rows per sample: thousands of adds on the same C addresses serialise in L2 otherwise; dsum_*: the per-channel sums

@@ -533,7 +533,8 @@ extern "C" int fsraft_altcorr_fwd(const float* fmap1, const float* fmap2, const 
 extern "C" int fsraft_altcorr_bwd(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
                                   float* fmap1_grad, float* fmap2_grad, int B, int N, int H1, int W1, int H2, int W2,
                                   int C, int radius, hipStream_t stream) {
-  if (!fmap1 || !fmap2 || !coords || !corr_grad || !fmap1_grad || !fmap2_grad || B < 1 || N < 1 || C < 1 || C > 64 * MAXK)
+  if (!fmap1 || !fmap2 || !coords || !corr_grad || !fmap1_grad || !fmap2_grad || B < 1 || N < 1 || H1 < 1 || W1 < 1 || H2 < 1 ||
+      W2 < 1 || C < 1 || C > 64 * MAXK)
     return FS_ERR_ARG;
   const int64_t nq = (int64_t)B * H1 * W1;
   dim3 grid((unsigned)((nq + 3) / 4));
@@ -554,17 +555,19 @@ extern "C" int fsraft_altcorr_fused_fwd(const float* fmap1, const float* const* 
     return FS_ERR_ARG;
   AltLevels lv;
   int h = H, w = W;
+  bool aligned = ((uintptr_t)fmap1 % 16) == 0;            // the tile kernel reads fmap1 and every level as f32x4
   for (int l = 0; l < 4; ++l) {
     lv.f2[l] = l < num_levels ? fmap2_levels[l] : nullptr;
     lv.h[l] = h; lv.w[l] = w;
     if (l < num_levels && (!fmap2_levels[l] || h < 1 || w < 1)) return FS_ERR_ARG;
+    if (l < num_levels && ((uintptr_t)fmap2_levels[l] % 16) != 0) aligned = false;
     h /= 2; w /= 2;
   }
   AltCoords co{coords, coords_bs, coords_cs, coords_ps, add_grid ? W : 0};
   const int64_t nq = (int64_t)B * H * W;
   dim3 grid((unsigned)((nq + 3) / 4));
   const float scale = 1.0f / sqrtf((float)C);
-  if (g_alt_tile && C % 64 == 0 && C <= 256 && ((uintptr_t)fmap1 % 16) == 0) {
+  if (g_alt_tile && C % 64 == 0 && C <= 256 && aligned) {
     dim3 tg((unsigned)(((W + AT_TQ - 1) / AT_TQ) * ((H + AT_TQ - 1) / AT_TQ)), (unsigned)B);
     if (radius == 4) hipLaunchKernelGGL(altcorr_tile_fwd_kernel<4>, tg, dim3(1024), 0, stream, fmap1, lv, co, out, num_levels, H, W, C, scale);
     else if (radius == 3) hipLaunchKernelGGL(altcorr_tile_fwd_kernel<3>, tg, dim3(1024), 0, stream, fmap1, lv, co, out, num_levels, H, W, C, scale);

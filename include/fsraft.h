@@ -154,14 +154,17 @@ int fsraft_corr_lookup_dcoords(float* const* levels, int num_levels, const float
 int fsraft_altcorr_fwd(const float* fmap1, const float* fmap2, const float* coords, float* corr, int B, int N, int H1,
                        int W1, int H2, int W2, int C, int radius, hipStream_t stream);
 /* fmap1_grad [B,H1,W1,C] is overwritten; fmap2_grad [B,H2,W2,C] must be zeroed by the caller
- * (it is accumulated with atomics); coords get no gradient (the reference returns zeros). */
+ * (it is accumulated with atomics); coords get no gradient (the reference returns zeros).
+ * Both entries: radius 3 or 4, B, N, H1, W1, H2, W2 >= 1, 1 <= C <= 256, no null pointer, else FSRAFT_ERR_ARG and nothing
+ * is written. */
 int fsraft_altcorr_bwd(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
                        float* fmap1_grad, float* fmap2_grad, int B, int N, int H1, int W1, int H2, int W2, int C,
                        int radius, hipStream_t stream);
 
 /* AlternateCorrBlock.__call__ (pytorch/core/corr.py:74-91: four alt_cuda_corr.forward calls, stack, reshape, / sqrt(C)) as ONE
  * launch that writes the channels-last [B,H,W,L*(2r+1)^2] lookup: fmap1 [B,H,W,C], fmap2_levels[l] [B,H>>l,W>>l,C] (the
- * average-pooled maps), coords as in fsraft_corr_lookup_tiled_fwd. */
+ * average-pooled maps), coords as in fsraft_corr_lookup_tiled_fwd.  The tile kernel (C a multiple of 64) reads the maps 16
+ * bytes at a time: a call whose fmap1 or any level is not 16-byte aligned is served by the wave-per-query kernel. */
 int fsraft_altcorr_fused_fwd(const float* fmap1, const float* const* fmap2_levels, int num_levels, const float* coords,
                              int64_t coords_bs, int64_t coords_cs, int64_t coords_ps, int add_grid, float* out, int B, int H, int W,
                              int C, int radius, hipStream_t stream);

@@ -16,6 +16,7 @@ on CPU tensors, forward raises.
 """
 import os
 import weakref
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
@@ -85,12 +86,7 @@ def _pad4(c):
     return (c + 3) // 4 * 4
 
 
-# measured: +2 % at best, and it makes per-kernel event timing meaningless (kernels of the two streams
-# overlap), so weight gradients stay on the main stream unless asked for
-_WGRAD_SIDE_STREAM = False
 FLOW_BRANCH_STREAM = True     # the motion encoder's flow branch on a second stream beside its correlation branch (forward): +0.6 % config 3, +1.5 % at one pair
-# one weight-gradient launch per layer per step (all iterations' operands stashed) instead of one per iteration
-_DEFER_WGRAD = True
 
 
 # --------------------------------------------------------------------------- layer table
@@ -105,6 +101,54 @@ class _Layer:
         self.kh, self.kw = kh, kw
         self.src_c = src_c          # channel counts of the concatenated inputs
         self.view_as = view_as      # (Cin, kh, kw) to reinterpret the OIHW weight (7x7 conv as 1x1 over im2col)
+
+
+# packed weights of one layer: forward / data-gradient images (the *_split ones for the split arithmetic), bias, Cout, OIHW shape
+_Pack = namedtuple("_Pack", "fwd dgrad bias cout shape fwd_split dgrad_split")
+
+
+class _Packs(dict):
+    """{layer key: _Pack} of one parameter version, plus the parameters the kernels read as they are."""
+    __slots__ = ("fh2_raw", "gamma")       # flow_head.conv2 (weight, bias) in OIHW; aggregator.gamma (GMA) or None
+
+
+class _Saved:
+    """What a recorded forward call keeps for its backward: the activations, and the per-step batches it wrote into."""
+    __slots__ = ("B", "H", "W", "corr", "cor1", "corflo", "cols", "flo1", "motion", "gates", "hlast", "head", "attn", "v", "agg",
+                 "attn_r", "mb", "hb", "gs")       # mb / hb: (MotionBatch / HeadBatch, slot); gs: grad_samples
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+class _Bwd:
+    """One backward call: its pixel grid, the packed weights and the gradient arena, and the launches every stage shares."""
+
+    def __init__(self, eng, P, st, B, H, W, dev):
+        self.eng, self.P, self.st, self.B, self.H, self.W, self.dev = eng, P, st, B, H, W, dev
+        self.dW, self.dB = eng._grad_arena(st, P, dev)
+
+    def buf(self, c, zero=False):
+        ld = _pad4(c)
+        if zero or ld != c:
+            return ops.zeros(self.B, self.H, self.W, ld, device=self.dev)
+        return torch.empty(self.B, self.H, self.W, ld, device=self.dev, dtype=torch.float32)
+
+    def wgrad(self, k, dy, srcs):
+        if self.st.pending is not None:
+            # deferred: dW = sum over the iterations of a step is one launch per layer, issued when the arena is
+            # unpacked (the operands stay alive, and are not written again, until then)
+            self.st.pending.setdefault((k, self.B, self.H, self.W), []).append((dy, srcs))
+            return
+        # frozen parameters: launched into an arena nobody unpacks (skipping it is a speed question of its own)
+        l = self.eng.layers[k]
+        ops.conv_wgrad(dy, srcs, self.dW[k], self.B, self.H, self.W, l.kh, l.kw, dbias=self.dB[k])
+
+    def dgrad(self, k, dy, dsts, alpha=1.0):
+        l, p = self.eng.layers[k], self.P[k]
+        ops.conv_forward([dy], p.dgrad, None, self.B, self.H, self.W, l.kh, l.kw, sum(l.src_c), dsts, alpha=alpha,
+                         wpk_split=p.dgrad_split)
 
 
 class _Engine:
@@ -189,29 +233,19 @@ class _Engine:
 
     def _grad_arena(self, st, P, dev):
         if st.arena is None:
-            sizes = [(k, P[k][0].numel(), P[k][3] if self.layers[k].bias else 0) for k in self.order]
+            sizes = [(k, P[k].fwd.numel(), P[k].cout if self.layers[k].bias else 0) for k in self.order]
             total = sum((a + 3) // 4 * 4 + (b + 3) // 4 * 4 for _, a, b in sizes) + 4 * len(self.extra)
             st.arena = torch.zeros(total, device=dev, dtype=torch.float32)
             st.dW, st.dB, o = {}, {}, 0
             for k, a, b in sizes:
-                st.dW[k] = st.arena[o:o + a].view_as(P[k][0]); o += (a + 3) // 4 * 4
+                st.dW[k] = st.arena[o:o + a].view_as(P[k].fwd); o += (a + 3) // 4 * 4
                 st.dB[k] = st.arena[o:o + b] if b else None; o += (b + 3) // 4 * 4
             for n in self.extra:
                 st.dB[n] = st.arena[o:o + 1]; o += 4
         return st.dW, st.dB
 
-    def _side_stream(self, dev):
-        s = self.__dict__.get("_side")
-        if s is None or s.device != dev:
-            s = torch.cuda.Stream(device=dev)
-            self.__dict__["_side"] = s
-        return s
-
     def unpack_param_grads(self, st, P, params):
         """packed arena -> list of gradients in self.pnames order (fused layers split back)."""
-        if _WGRAD_SIDE_STREAM and st.arena is not None:
-            torch.cuda.current_stream(st.arena.device).wait_stream(self._side_stream(st.arena.device))
-        st.keep = None
         if st.pending:
             dW, dB = self._grad_arena(st, P, params[0].device)
             for (k, B, H, W), lst in st.pending.items():
@@ -259,19 +293,18 @@ class _Engine:
         return [sd[n] for n in self.pnames]
 
     def _packed(self, params):
-        """{key: (wpk_fwd, wpk_dgrad, bias, out_channels, oihw_shape)}; repacked when any parameter changed."""
+        """The _Packs of `params`; repacked when any parameter changed."""
         key = (ops.exact_mode(),) + tuple((p.data_ptr(), p._version) for p in params)      # (the mode decides which packs exist)
         if key == self._cache_key:
             return self._cache
         byname = dict(zip(self.pnames, params))
-        out = {}
+        out = _Packs()
         exact = ops.exact_mode()
         with torch.no_grad():
-            for n in self.extra:
-                out[n] = byname[n].detach().float().reshape(-1)
+            out.gamma = byname["aggregator.gamma"].detach().float().reshape(-1) if self.gma else None
             # the 2-output flow-head convolution runs on the dot-product kernels straight from the OIHW weight
-            out["fh2.raw"] = (byname["flow_head.conv2.weight"].detach().contiguous().float(),
-                              byname["flow_head.conv2.bias"].detach().contiguous().float())
+            out.fh2_raw = (byname["flow_head.conv2.weight"].detach().contiguous().float(),
+                           byname["flow_head.conv2.bias"].detach().contiguous().float())
             # every packed matrix of the block in one batched launch, read in place from the parameters (fused layers and the
             # (h, motion) / context split of the GRU weights are address arithmetic of fsraft_pack_conv_weights)
             plan = ops.PackPlan(params[0].device)
@@ -291,10 +324,11 @@ class _Engine:
                 if l.bias:
                     bs = [byname[w_ + ".bias"].detach().contiguous().float() for w_ in l.wnames]
                     b = bs[0] if len(bs) == 1 else plan.bias(bs)
-                handles[k] = (fw, dg, b, cout, (cout, cin, kh, kw), fws, dgs)
+                handles[k] = _Pack(fw, dg, b, cout, (cout, cin, kh, kw), fws, dgs)
             packed = plan.run()
-            for k, (fw, dg, b, cout, shape, fws, dgs) in handles.items():
-                out[k] = (packed[fw], packed[dg], packed[b] if isinstance(b, int) else b, cout, shape, packed[fws], packed[dgs])
+            for k, h in handles.items():        # (plan handles -> the packed tensors)
+                out[k] = h._replace(fwd=packed[h.fwd], dgrad=packed[h.dgrad], bias=packed[h.bias] if isinstance(h.bias, int) else h.bias,
+                                    fwd_split=packed[h.fwd_split], dgrad_split=packed[h.dgrad_split])
         self._cache_key, self._cache = key, out
         return out
 
@@ -306,10 +340,10 @@ class _Engine:
         P = self._packed(params)
         out = {}
         for k in self.ctx_keys:
-            l = self.layers[k]
-            buf = torch.empty(B, H, W, P[k][3], device=inp.device, dtype=torch.float32)
-            ops.conv_forward([V(inp, self.inp_c)], P[k][0], P[k][2], B, H, W, l.kh, l.kw, P[k][3], [Dst.nhwc(buf)],
-                             wpk_split=P[k][5])
+            l, p = self.layers[k], P[k]
+            buf = torch.empty(B, H, W, p.cout, device=inp.device, dtype=torch.float32)
+            ops.conv_forward([V(inp, self.inp_c)], p.fwd, p.bias, B, H, W, l.kh, l.kw, p.cout, [Dst.nhwc(buf)],
+                             wpk_split=p.fwd_split)
             out[k] = buf
         return out
 
@@ -332,11 +366,10 @@ class _Engine:
                 ops.sum_n_(parts, g, accumulate=cst.dsum.get(k) is not None)
             if g is None:
                 continue
-            l = self.layers[k]
-            n = P[k][3]
-            ops.conv_wgrad(V(g, n), [V(inp, self.inp_c)], dW[k], B, H, W, l.kh, l.kw, dbias=dB[k])
-            ops.conv_forward([V(g, n)], P[k][1], None, B, H, W, l.kh, l.kw, self.inp_c, [Dst.nhwc(dinp, 0, 0, acc)],
-                             wpk_split=P[k][6])
+            l, p = self.layers[k], P[k]
+            ops.conv_wgrad(V(g, p.cout), [V(inp, self.inp_c)], dW[k], B, H, W, l.kh, l.kw, dbias=dB[k])
+            ops.conv_forward([V(g, p.cout)], p.dgrad, None, B, H, W, l.kh, l.kw, self.inp_c, [Dst.nhwc(dinp, 0, 0, acc)],
+                             wpk_split=p.dgrad_split)
             acc = True
         if not acc:
             dinp.zero_()
@@ -347,7 +380,7 @@ class _Engine:
     def forward(self, net, ctxb, corr, flow, params, save, attn=None, attn_t=None, need_mask=True, head_out=None, mslot=None, hlast_out=None):
         """net/corr: channels-last [B,H,W,C]; ctxb: context() of the context features; flow: [B,2,H,W] (any pixel stride).
         Returns (net_out [B,H,W,hid], mask [B,H,W,576] or None, delta [B,2,H,W]) and, if `save`,
-        a dict of the intermediates backward needs.  need_mask=False (inference, every iteration but the last: the
+        the _Saved intermediates backward needs.  need_mask=False (inference, every iteration but the last: the
         reference computes the mask each time and drops it, raft.py:134-139) skips the 256 -> 576 mask convolution."""
         L.require_cuda_f32(net, corr, flow)
         B, H, W, _ = net.shape
@@ -361,10 +394,9 @@ class _Engine:
             return torch.empty(B, H, W, ld, device=dev, dtype=torch.float32)
 
         def conv(k, srcs, dsts, relu=False, alpha=1.0, **kw):
-            l = self.layers[k]
-            wpk, _, bias, n = P[k][:4]
-            ops.conv_forward(srcs, wpk, bias, B, H, W, l.kh, l.kw, n, dsts, relu=relu, alpha=alpha,
-                             wpk_split=P[k][5], **kw)
+            l, p = self.layers[k], P[k]
+            ops.conv_forward(srcs, p.fwd, p.bias, B, H, W, l.kh, l.kw, p.cout, dsts, relu=relu, alpha=alpha,
+                             wpk_split=p.fwd_split, **kw)
 
         hid = self.hid
         if mslot is not None:
@@ -426,7 +458,7 @@ class _Engine:
                                     ksplit=2)
             else:
                 ops.gemm_raw(attn.data_ptr(), N, N * N, v.data_ptr(), mc, N * mc, agg.data_ptr(), mc, N * mc, B, N, mc, N, False)
-            ops.gma_mix_fwd(V(motion, mc, 0), V(agg), P["aggregator.gamma"], V(motion, mc, mc))
+            ops.gma_mix_fwd(V(motion, mc, 0), V(agg), P.gamma, V(motion, mc, mc))
 
         h = net
         gates = []
@@ -446,7 +478,7 @@ class _Engine:
         conv("hd", [V(h, hid)], [Dst.nhwc(head)], relu=True)
         delta = torch.empty(B, 2, H, W, device=dev, dtype=torch.float32)
         if self.head_c % 4 == 0 and self.head_c <= 512:
-            ops.conv_small_fwd(V(head, self.head_c), P["fh2.raw"][0], P["fh2.raw"][1], delta)
+            ops.conv_small_fwd(V(head, self.head_c), P.fh2_raw[0], P.fh2_raw[1], delta)
         else:
             conv("fh2", [V(head, self.head_c)], [Dst.nchw(delta)])
         mask = None
@@ -455,205 +487,53 @@ class _Engine:
             conv("m2", [V(head, self.head_c, self.head_c)], [Dst.nhwc(mask)], alpha=0.25)
         saved = None
         if save:
-            saved = dict(B=B, H=H, W=W, corr=corr, cor1=cor1, corflo=corflo, cols=cols, flo1=flo1,
-                         motion=motion, gates=gates, hlast=h, head=head, attn=attn, v=v, agg=agg, attn_r=attn_t)
+            saved = _Saved(B=B, H=H, W=W, corr=corr, cor1=cor1, corflo=corflo, cols=cols, flo1=flo1,
+                           motion=motion, gates=gates, hlast=h, head=head, attn=attn, v=v, agg=agg, attn_r=attn_t)
         return h, mask, delta, saved
 
     # ---- backward -----------------------------------------------------------------
-    def backward(self, S, P, st, dnet_out, dmask, ddelta, need_input_grads=True, ast=None, cst=None, need_dflow=True, motion_only=None, heads_only=False):
-        """Accumulates parameter gradients into the packed arena of `st` and the gate gradients into `cst.dsum`
-        (the context part's backward runs once per step, context_backward); returns (dnet, dcorr, dflow)."""
-        B, H, W = S["B"], S["H"], S["W"]
-        dev = S["corr"].device
-        lib = L.load()
+    def backward(self, S, P, st, dnet_out, dmask, ddelta, need_input_grads=True, ast=None, cst=None, need_dflow=True):
+        """One iteration's backward from its _Saved state: heads, GRU passes, Aggregate, motion encoder (the stages below), less what
+        the per-step batches of `S` do once for all iterations.  Accumulates parameter gradients into the packed arena of `st` and
+        the gate gradients into `cst.dsum` (the context part's backward runs once per step, context_backward); returns
+        (dnet, dcorr, dflow)."""
+        B = Bf = S.B
         # grad_samples (forward_cl): the caller vouches that only the first k samples of the batch receive gradient from its
         # loss (the flow-supervisor step batches a labelled and an unlabelled sample; the supervisor's predictions of the
         # unlabelled one carry none).  Every buffer is sample-major, so the whole backward simply runs on B = k: the kernels read
         # the first k samples of the saved activations and of the incoming gradients; what goes back to autograd (dnet, dcorr)
         # and the context part's running sums are full-size with zeros behind sample k.
-        Bf = B
-        gs = S.get("gs")
-        if gs is not None and 0 < gs < Bf and (not self.gma or ast is None) and not need_dflow and motion_only is None and not heads_only:
-            B = gs
-            dnet_out = dnet_out[:B] if dnet_out is not None else None
-            ddelta = ddelta[:B] if ddelta is not None else None
-            dmask = dmask[:B] if dmask is not None else None
-        M = B * H * W
-        hid = self.hid
-
-        def buf(c, zero=False):
-            ld = _pad4(c)
-            if zero or ld != c:
-                return ops.zeros(B, H, W, ld, device=dev)
-            return torch.empty(B, H, W, ld, device=dev, dtype=torch.float32)
-
-        dW, dB = self._grad_arena(st, P, dev)
-        if st.keep is None:
-            st.keep = []
-
-        def relu_bwd(g, y):
-            L.check(lib.fsraft_relu_bwd(L.c_void_p(g.ptr), g.ld, L.c_void_p(y.ptr), y.ld, M, g.C, L.stream()), "relu_bwd")
-
-        # Weight gradients run on a side stream, concurrently with the data-gradient chain on the
-        # main stream: the two only share read-only inputs, and co-scheduling them fills the CUs a
-        # single 220..880-workgroup GEMM leaves idle in its last wave.  Everything the side stream
-        # reads is kept alive in st.keep until the arena is unpacked (which joins the streams).
-        side = self._side_stream(dev) if _WGRAD_SIDE_STREAM else None
-        main = torch.cuda.current_stream(dev)
-        keep = st.keep if st.keep is not None else []
-
-        def wgrad(k, dy, srcs):
-            l = self.layers[k]
-            if st.pending is not None:
-                # deferred: dW = sum over the iterations of a step is one launch per layer, issued when the arena is
-                # unpacked (the operands stay alive, and are not written again, until then)
-                st.pending.setdefault((k, B, H, W), []).append((dy, srcs))
-                return
-            if side is None:
-                ops.conv_wgrad(dy, srcs, dW[k], B, H, W, l.kh, l.kw, dbias=dB[k])
-                return
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            keep.append((dy.t, [v.t for v in srcs]))
-            with torch.cuda.stream(side):
-                ops.conv_wgrad(dy, srcs, dW[k], B, H, W, l.kh, l.kw, dbias=dB[k])
-
-        def dgrad(k, dy, dsts, alpha=1.0):
-            l = self.layers[k]
-            n_in = sum(l.src_c)
-            ops.conv_forward([dy], P[k][1], None, B, H, W, l.kh, l.kw, n_in, dsts, alpha=alpha, wpk_split=P[k][6])
-
-        dh = dh_full = None
-        mbs = S.get("mb")             # (MotionBatch, slot): the motion encoder's backward of all iterations runs once, after slot 0's
-        if motion_only is not None:
-            dmotion, motion = motion_only, S["motion"]
-        if motion_only is None:
-            # ---- heads
-            hb = S.get("hb")
-            dh_more = None
-            if hb is not None and hb[0].heads_done:
-                # the whole head backward of this iteration (flow head, mask head, the 3x3 convolution under both) already ran, for
-                # all iterations at once, inside the batched backward of the mask head + upsampler (_MaskUpFn): it depends on the
-                # loss alone, not on the recurrence.  What is left is to add the hidden-state gradient arriving from iteration t + 1.
-                dh = hb[0].dh_heads[hb[1]][:B]
-                if ddelta is not None and ddelta.data_ptr() != hb[0].dflow[hb[1]].data_ptr():
-                    raise RuntimeError("HeadBatch: an iteration's delta_flow received a gradient from somewhere other than its prediction")
-                dh_more = dnet_out.contiguous() if dnet_out is not None else None      # (added inside the first gate-gradient kernel)
+        if S.gs is not None and 0 < S.gs < Bf and (not self.gma or ast is None) and not need_dflow:
+            B = S.gs
+            dnet_out, dmask, ddelta = (g[:B] if g is not None else None for g in (dnet_out, dmask, ddelta))
+        c = _Bwd(self, P, st, B, S.H, S.W, S.corr.device)
+        hb, mbs = S.hb, S.mb
+        dh_more = None
+        if hb is not None and hb[0].heads_done:
+            # the whole head backward of this iteration (flow head, mask head, the 3x3 convolution under both) already ran, for
+            # all iterations at once, inside the batched backward of the mask head + upsampler (_MaskUpFn): it depends on the
+            # loss alone, not on the recurrence.  What is left is to add the hidden-state gradient arriving from iteration t + 1.
+            dh = hb[0].dh_heads[hb[1]][:B]
+            if ddelta is not None and ddelta.data_ptr() != hb[0].dflow[hb[1]].data_ptr():
+                raise RuntimeError("HeadBatch: an iteration's delta_flow received a gradient from somewhere other than its prediction")
+            dh_more = dnet_out.contiguous() if dnet_out is not None else None      # (added inside the first gate-gradient kernel)
+        else:
+            if hb is not None:
+                # the mask half of dhead was written by the batched backward of the mask head (HeadBatch / _MaskUpFn), which
+                # autograd runs before this node: this iteration's delta gradient comes out of it
+                dhead = hb[0].dhead_slot(hb[1])[:B]
             else:
-                head = S["head"]
-                if heads_only:
-                    dhead = S["dhead"]
-                elif hb is not None:
-                    # the mask half of dhead was written by the batched backward of the mask head (HeadBatch / _MaskUpFn), which
-                    # autograd runs before this node: this iteration's delta gradient comes out of it
-                    dhead = hb[0].dhead_slot(hb[1])[:B]
-                else:
-                    dhead = buf(self.head_c * (2 if self.has_mask else 1))
-                if self.has_mask and hb is None and not heads_only:
-                    if dmask is not None:
-                        # y = 0.25*(Wx+b)  =>  everything upstream sees 0.25*dmask: the data gradient applies the factor in its
-                        # epilogue, the weight / bias gradients once per step when the arena is unpacked
-                        g = dmask.contiguous()
-                        wgrad("m2", V(g, 576), [V(head, self.head_c, self.head_c)])
-                        dgrad("m2", V(g, 576), [Dst.nhwc(dhead, self.head_c).masked(V(head, self.head_c, self.head_c))], alpha=0.25)
-                    else:
-                        dhead[..., self.head_c:].zero_()
-                dd = ops.zeros(B, H, W, 4, device=dev)
-                if ddelta is not None:
-                    ops.flow_to_nhwc(ddelta, dd, 0)
-                    wgrad("fh2", V(dd, 2), [V(head, self.head_c)])
-                    if FH2_DGRAD_SMALL and "fh2.raw" in P and self.head_c % 4 == 0 and self.head_c <= 256:
-                        # 18 multiply-adds per element: a streaming kernel, not an implicit GEMM with K padded from 18 to 288
-                        ops.conv_small_dgrad(V(dd, 2), P["fh2.raw"][0], V(dhead, self.head_c, 0), V(head, self.head_c, 0), B, H, W)
-                    else:
-                        dgrad("fh2", V(dd, 2), [Dst.nhwc(dhead, 0).masked(V(head, self.head_c, 0))])
-                else:
-                    dhead[..., : self.head_c].zero_()
-                # (no separate ReLU-backward pass: the two data-gradient epilogues above wrote dhead already masked by head > 0)
-                hlast = S["hlast"]
-                wgrad("hd", V(dhead), [V(hlast, hid)])
-                dh = S["dh_out"] if heads_only else buf(hid)
-                if dnet_out is not None:
-                    dh.copy_(dnet_out)
-                    dgrad("hd", V(dhead), [Dst.nhwc(dh, 0, 0, True)])
-                else:
-                    dgrad("hd", V(dhead), [Dst.nhwc(dh)])
-                if heads_only:
-                    return None, None, None
-
-            # ---- GRU passes, last to first
-            motion = S["motion"]
-            # every GRU data gradient adds its motion part; the first one (the q convolution of the last pass covers all x_c
-            # channels) overwrites instead, so the buffer needs no zero fill -- only its padding channels, if any, do
-            dmotion = mbs[0].dmotion[mbs[1]][:B] if mbs is not None else buf(self.x_c)
-            dm_first = [True]
-
-            def dm_acc():
-                first, dm_first[0] = dm_first[0], False
-                return not first
-
-            def ctx_sum(k, like):
-                """Running sum of the gate gradients over the iterations of the step (filled by the gru_bwd kernels) -- or, deferred:
-                the iteration's buffer is only noted and context_backward adds the kept buffers up in one pass."""
-                if cst is None:
-                    return None
-                if CTX_SUM_DEFERRED:
-                    cst.parts.setdefault(k, []).append(like)
-                    return None
-                if k not in cst.dsum:
-                    cst.dsum[k] = ops.zeros((Bf,) + tuple(like.shape[1:]), device=like.device)
-                return cst.dsum[k]
-
-            first_pass = self.passes[0][0]
-            for (sfx, _, _), (h, z, r, rh, q) in reversed(list(zip(self.passes, S["gates"]))):
-                dzr = buf(2 * hid)
-                dq = buf(hid)
-                if B != Bf and sfx == first_pass:          # the buffer that goes back to autograd as dnet: full size, zeros behind sample B
-                    dh_full = ops.zeros(Bf, H, W, _pad4(hid), device=dev)
-                    dhp = dh_full[:B]
-                else:
-                    dhp = buf(hid)
-                zsum, qsum = ctx_sum("zi" + sfx, dzr), ctx_sum("qi" + sfx, dq)
-                ops.gru_bwd1(dh, z, q, h, dzr, dq, dhp, hid, zsum, qsum, dhn2=dh_more)
-                dh_more = None
-                xs = [V(motion, self.x_c)]
-                wgrad("q" + sfx, V(dq, hid), [V(rh, hid)] + xs)
-                drh = buf(hid)
-                dgrad("q" + sfx, V(dq, hid), [Dst.nhwc(drh, 0, 0), Dst.nhwc(dmotion, 0, hid, dm_acc())])
-                ops.gru_bwd2(drh, r, h, dzr, dhp, hid, zsum)
-                wgrad("zr" + sfx, V(dzr, 2 * hid), [V(h, hid)] + xs)
-                dm = Dst.nhwc(dmotion, 0, hid, True)
-                if sfx == first_pass and not self.gma:
-                    # last accumulation into dmotion: its epilogue applies the motion encoder's ReLU backward to the conv
-                    # channels [0, cv) (the two flow channels behind them pass through)
-                    dm = dm.masked(V(motion, self.cv))
-                dgrad("zr" + sfx, V(dzr, 2 * hid), [Dst.nhwc(dhp, 0, 0, True), dm])
-                dh = dhp
-
-            # ---- Aggregate (GMA): motion_global = motion + gamma * (attn @ to_v(motion))
-            if self.gma:
-                N, mc = H * W, self.mot_c
-                attn, v, agg = S["attn"], S["v"], S["agg"]
-                dagg, dv = buf(mc), buf(mc)
-                ops.gma_mix_bwd(V(dmotion, mc, mc), V(agg), P["aggregator.gamma"], V(dmotion, mc, 0), V(dagg),
-                                dB["aggregator.gamma"])
-                attn_r = S.get("attn_r")
-                if attn_r is not None:   # dv = attn^T dagg: both operands k-major records -> transposed-read record GEMM
-                    Nr = attn_r.shape[-1]
-                    dr = ops.to_records(dagg.view(B, N, mc))
-                    ops.gemm_rec_tn_raw(attn_r.data_ptr(), Nr, N * Nr, dr.data_ptr(), dr.shape[-1], N * dr.shape[-1], dv.data_ptr(), mc,
-                                        N * mc, B, N, mc, N, ksplit=2)
-                elif N % 4 == 0:     # (exact-fp32 test mode) both operands k-major -> transposed-read split GEMM
-                    ops.gemm_tn_raw(attn.data_ptr(), N, N * N, dagg.data_ptr(), mc, N * mc, dv.data_ptr(), mc, N * mc, B, N, mc, N)
-                else:
-                    at = attn.view(B, N, N).transpose(1, 2).contiguous()
-                    ops.gemm_raw(at.data_ptr(), N, N * N, dagg.data_ptr(), mc, N * mc, dv.data_ptr(), mc, N * mc, B, N, mc, N, False)
-                if ast is not None:  # dattn = sum_t dagg_t v_t^T is formed once per step from the stashed factors
-                    ast.stash.append((dagg.view(B, N, mc), v.view(B, N, mc)))
-                wgrad("av", V(dv, mc), [V(motion, mc, 0)])
-                dgrad("av", V(dv, mc), [Dst.nhwc(dmotion, 0, 0, True)])
-
+                dhead = c.buf(self.head_c * (2 if self.has_mask else 1))
+                if self.has_mask:
+                    self.bwd_mask_head(c, S.head, dmask, dhead)
+            dh = c.buf(self.hid)
+            self.bwd_heads(c, S.head, S.hlast, dhead, ddelta, dnet_out, dh)
+        # every GRU data gradient adds its motion part; the first one (the q convolution of the last pass covers all x_c
+        # channels) overwrites instead, so the buffer needs no zero fill -- only its padding channels, if any, do
+        dmotion = mbs[0].dmotion[mbs[1]][:B] if mbs is not None else c.buf(self.x_c)
+        dnet = self.bwd_gru(c, S.gates, S.motion, dh, dh_more, dmotion, cst, Bf)
+        if self.gma:
+            self.bwd_aggregate(c, S.motion, S.attn, S.attn_r, S.v, S.agg, dmotion, ast)
         if mbs is not None:
             # deferred: this iteration's dmotion sits in its slot; the motion encoder's backward (four data gradients, five weight
             # gradients) runs for all slots at once when slot 0 -- the first iteration, the last to run backward -- has handed in
@@ -662,53 +542,147 @@ class _Engine:
             mb.parked.add(t)
             if t == 0:
                 mb.run(self, P, st)
-            return (dh_full if B != Bf else dh), mb.dcorr[t], None
+            return dnet, mb.dcorr[t], None
+        dcorr = None        # (what goes back to autograd: full size, zeros behind sample B)
+        if need_input_grads:
+            dcorr = ops.zeros(Bf, S.H, S.W, _pad4(self.corr_c), device=c.dev) if B != Bf else c.buf(self.corr_c)
+        dflow = self.bwd_motion(c, S, dmotion, dcorr[:B] if dcorr is not None else None, need_dflow)
+        return dnet, dcorr, dflow
 
-        # ---- motion encoder
+    def bwd_mask_head(self, c, head, dmask, dhead):
+        """Mask head of one iteration (no HeadBatch): dmask -> the mask half of dhead."""
+        hc = self.head_c
+        if dmask is not None:
+            # y = 0.25*(Wx+b)  =>  everything upstream sees 0.25*dmask: the data gradient applies the factor in its
+            # epilogue, the weight / bias gradients once per step when the arena is unpacked
+            g = dmask.contiguous()
+            c.wgrad("m2", V(g, 576), [V(head, hc, hc)])
+            c.dgrad("m2", V(g, 576), [Dst.nhwc(dhead, hc).masked(V(head, hc, hc))], alpha=0.25)
+        else:
+            dhead[..., hc:].zero_()
+
+    def bwd_heads(self, c, head, hlast, dhead, ddelta, dnet_out, dh):
+        """Flow head, then the 3x3 convolution under both heads: fills the flow half of dhead (its mask half is the caller's) and
+        writes dh = dnet_out + the convolution's data gradient.  One iteration, or all of a HeadBatch at once (_MaskUpFn)."""
+        hc = self.head_c
+        dd = ops.zeros(c.B, c.H, c.W, 4, device=c.dev)
+        if ddelta is not None:
+            ops.flow_to_nhwc(ddelta, dd, 0)
+            c.wgrad("fh2", V(dd, 2), [V(head, hc)])
+            if FH2_DGRAD_SMALL and hc % 4 == 0 and hc <= 256:
+                # 18 multiply-adds per element: a streaming kernel, not an implicit GEMM with K padded from 18 to 288
+                ops.conv_small_dgrad(V(dd, 2), c.P.fh2_raw[0], V(dhead, hc, 0), V(head, hc, 0), c.B, c.H, c.W)
+            else:
+                c.dgrad("fh2", V(dd, 2), [Dst.nhwc(dhead, 0).masked(V(head, hc, 0))])
+        else:
+            dhead[..., :hc].zero_()
+        # (no separate ReLU-backward pass: the two data-gradient epilogues above wrote dhead already masked by head > 0)
+        c.wgrad("hd", V(dhead), [V(hlast, self.hid)])
+        if dnet_out is not None:
+            dh.copy_(dnet_out)
+            c.dgrad("hd", V(dhead), [Dst.nhwc(dh, 0, 0, True)])
+        else:
+            c.dgrad("hd", V(dhead), [Dst.nhwc(dh)])
+
+    def bwd_gru(self, c, gates, motion, dh, dh_more, dmotion, cst, Bf):
+        """GRU passes, last to first, from dh (+ dh_more): adds the motion part of every data gradient into dmotion (the first
+        one overwrites), hands the gate gradients to `cst`, returns dnet [Bf,H,W,hid] (zeros behind sample c.B)."""
+        B, hid = c.B, self.hid
+
+        def ctx_sum(k, like):
+            """Running sum of the gate gradients over the iterations of the step (filled by the gru_bwd kernels) -- or, deferred:
+            the iteration's buffer is only noted and context_backward adds the kept buffers up in one pass."""
+            if cst is None:
+                return None
+            if CTX_SUM_DEFERRED:
+                cst.parts.setdefault(k, []).append(like)
+                return None
+            if k not in cst.dsum:
+                cst.dsum[k] = ops.zeros((Bf,) + tuple(like.shape[1:]), device=like.device)
+            return cst.dsum[k]
+
+        first_pass, dm_acc = self.passes[0][0], False
+        for (sfx, _, _), (h, z, r, rh, q) in reversed(list(zip(self.passes, gates))):
+            dzr = c.buf(2 * hid)
+            dq = c.buf(hid)
+            if B != Bf and sfx == first_pass:          # the buffer that goes back to autograd as dnet: full size, zeros behind sample B
+                dnet = ops.zeros(Bf, c.H, c.W, _pad4(hid), device=c.dev)
+                dhp = dnet[:B]
+            else:
+                dnet = dhp = c.buf(hid)
+            zsum, qsum = ctx_sum("zi" + sfx, dzr), ctx_sum("qi" + sfx, dq)
+            ops.gru_bwd1(dh, z, q, h, dzr, dq, dhp, hid, zsum, qsum, dhn2=dh_more)
+            dh_more = None
+            xs = [V(motion, self.x_c)]
+            c.wgrad("q" + sfx, V(dq, hid), [V(rh, hid)] + xs)
+            drh = c.buf(hid)
+            c.dgrad("q" + sfx, V(dq, hid), [Dst.nhwc(drh, 0, 0), Dst.nhwc(dmotion, 0, hid, dm_acc)])
+            dm_acc = True
+            ops.gru_bwd2(drh, r, h, dzr, dhp, hid, zsum)
+            c.wgrad("zr" + sfx, V(dzr, 2 * hid), [V(h, hid)] + xs)
+            dm = Dst.nhwc(dmotion, 0, hid, True)
+            if sfx == first_pass and not self.gma:
+                # last accumulation into dmotion: its epilogue applies the motion encoder's ReLU backward to the conv
+                # channels [0, cv) (the two flow channels behind them pass through)
+                dm = dm.masked(V(motion, self.cv))
+            c.dgrad("zr" + sfx, V(dzr, 2 * hid), [Dst.nhwc(dhp, 0, 0, True), dm])
+            dh = dhp
+        return dnet
+
+    def bwd_aggregate(self, c, motion, attn, attn_r, v, agg, dmotion, ast):
+        """Aggregate (GMA): motion_global = motion + gamma * (attn @ to_v(motion)); folds dmotion's global half into its local one
+        and stashes the factors of dattn in `ast`."""
+        B, N, mc = c.B, c.H * c.W, self.mot_c
+        dagg, dv = c.buf(mc), c.buf(mc)
+        ops.gma_mix_bwd(V(dmotion, mc, mc), V(agg), c.P.gamma, V(dmotion, mc, 0), V(dagg), c.dB["aggregator.gamma"])
+        if attn_r is not None:   # dv = attn^T dagg: both operands k-major records -> transposed-read record GEMM
+            Nr = attn_r.shape[-1]
+            dr = ops.to_records(dagg.view(B, N, mc))
+            ops.gemm_rec_tn_raw(attn_r.data_ptr(), Nr, N * Nr, dr.data_ptr(), dr.shape[-1], N * dr.shape[-1], dv.data_ptr(), mc,
+                                N * mc, B, N, mc, N, ksplit=2)
+        elif N % 4 == 0:     # (exact-fp32 test mode) both operands k-major -> transposed-read split GEMM
+            ops.gemm_tn_raw(attn.data_ptr(), N, N * N, dagg.data_ptr(), mc, N * mc, dv.data_ptr(), mc, N * mc, B, N, mc, N)
+        else:
+            at = attn.view(B, N, N).transpose(1, 2).contiguous()
+            ops.gemm_raw(at.data_ptr(), N, N * N, dagg.data_ptr(), mc, N * mc, dv.data_ptr(), mc, N * mc, B, N, mc, N, False)
+        if ast is not None:  # dattn = sum_t dagg_t v_t^T is formed once per step from the stashed factors
+            ast.stash.append((dagg.view(B, N, mc), v.view(B, N, mc)))
+        c.wgrad("av", V(dv, mc), [V(motion, mc, 0)])
+        c.dgrad("av", V(dv, mc), [Dst.nhwc(dmotion, 0, 0, True)])
+
+    def bwd_motion(self, c, A, dmotion, dcorr, need_dflow):
+        """Motion encoder over the activations A (corr, cor1, corflo, cols, flo1, motion: one iteration's _Saved, or a MotionBatch's
+        slots as one batch) from dmotion; writes the correlation gradient into dcorr unless None, returns dflow or None."""
         # (the loops detach the flow that enters an iteration, raft.py:123: its gradient -- the pass-through channels of the
         #  motion features plus the 7x7 convolution's data gradient -- is then three launches per iteration nobody reads)
-        dflow = torch.empty(B, 2, H, W, device=dev, dtype=torch.float32) if need_dflow else None
+        dflow = torch.empty(c.B, 2, c.H, c.W, device=c.dev, dtype=torch.float32) if need_dflow else None
         if need_dflow:
             ops.nhwc_to_flow(dmotion, self.cv, dflow, False)
         if self.gma:      # (GMA adds to dmotion after the GRU, so the mask cannot ride on a GRU epilogue)
-            relu_bwd(V(dmotion, self.cv), V(motion, self.cv))
-        corflo = S["corflo"]
-        wgrad("cv", V(dmotion, self.cv), [V(corflo, self.cf_c)])
-        dcorflo = buf(self.cf_c)
-        dgrad("cv", V(dmotion, self.cv), [Dst.nhwc(dcorflo).masked(V(corflo, self.cf_c))])
+            ops.relu_bwd_(dmotion, A.motion, self.cv)
+        c.wgrad("cv", V(dmotion, self.cv), [V(A.corflo, self.cf_c)])
+        dcorflo = c.buf(self.cf_c)
+        c.dgrad("cv", V(dmotion, self.cv), [Dst.nhwc(dcorflo).masked(V(A.corflo, self.cf_c))])
         cor_out = self.c2 if self.c2 else self.c1
-        flo1 = S["flo1"]
-        wgrad("f2", V(dcorflo, self.f2, cor_out), [V(flo1, self.f1)])
-        dflo1 = buf(self.f1)
-        dgrad("f2", V(dcorflo, self.f2, cor_out), [Dst.nhwc(dflo1).masked(V(flo1, self.f1))])
-        cols = S["cols"]
-        wgrad("f1", V(dflo1, self.f1), [V(cols, 98)])
+        c.wgrad("f2", V(dcorflo, self.f2, cor_out), [V(A.flo1, self.f1)])
+        dflo1 = c.buf(self.f1)
+        c.dgrad("f2", V(dcorflo, self.f2, cor_out), [Dst.nhwc(dflo1).masked(V(A.flo1, self.f1))])
+        c.wgrad("f1", V(dflo1, self.f1), [V(A.cols, 98)])
         if need_dflow:
-            dcols = torch.empty(B, H, W, _pad4(98), device=dev, dtype=torch.float32)     # (col2im7 reads the 98 channels only)
-            dgrad("f1", V(dflo1, self.f1), [Dst.nhwc(dcols)])
+            dcols = torch.empty(c.B, c.H, c.W, _pad4(98), device=c.dev, dtype=torch.float32)     # (col2im7 reads the 98 channels only)
+            c.dgrad("f1", V(dflo1, self.f1), [Dst.nhwc(dcols)])
             ops.col2im7(dcols, dflow, True)
-        corr = S["corr"]
-        dcorr = dcorr_full = None
-        if need_input_grads:
-            if motion_only is not None:
-                dcorr_full = S["dcorr_out"]
-            else:
-                dcorr_full = ops.zeros(Bf, H, W, _pad4(self.corr_c), device=dev) if B != Bf else buf(self.corr_c)
-            dcorr = dcorr_full[:B]
         if self.c2:
-            cor1 = S["cor1"]
-            wgrad("c2", V(dcorflo, self.c2, 0), [V(cor1, self.c1)])
-            dcor1 = buf(self.c1)
-            dgrad("c2", V(dcorflo, self.c2, 0), [Dst.nhwc(dcor1).masked(V(cor1, self.c1))])
-            wgrad("c1", V(dcor1, self.c1), [V(corr, self.corr_c)])
-            if need_input_grads:
-                dgrad("c1", V(dcor1, self.c1), [Dst.nhwc(dcorr)])
+            c.wgrad("c2", V(dcorflo, self.c2, 0), [V(A.cor1, self.c1)])
+            dcor1 = c.buf(self.c1)
+            c.dgrad("c2", V(dcorflo, self.c2, 0), [Dst.nhwc(dcor1).masked(V(A.cor1, self.c1))])
+            dcor = V(dcor1, self.c1)
         else:
-            wgrad("c1", V(dcorflo, self.c1, 0), [V(corr, self.corr_c)])
-            if need_input_grads:
-                dgrad("c1", V(dcorflo, self.c1, 0), [Dst.nhwc(dcorr)])
-
-        return (dh_full if B != Bf else dh), dcorr_full, dflow
+            dcor = V(dcorflo, self.c1, 0)
+        c.wgrad("c1", dcor, [V(A.corr, self.corr_c)])
+        if dcorr is not None:
+            c.dgrad("c1", dcor, [Dst.nhwc(dcorr)])
+        return dflow
 
 
 class _CtxState:
@@ -744,12 +718,13 @@ class _CtxFn(torch.autograd.Function):
 
 
 class _ParamState:
-    __slots__ = ("key", "anchor", "arena", "dW", "dB", "consumed", "zero", "keep", "pending")
+    __slots__ = ("key", "anchor", "arena", "dW", "dB", "consumed", "zero", "pending")
 
     def __init__(self, key):
         self.key, self.anchor, self.arena, self.dW, self.dB, self.consumed, self.zero = key, None, None, None, None, False, None
-        self.keep = None
-        self.pending = {} if (key is not None and _DEFER_WGRAD) else None     # frozen-parameter states compute nothing
+        # {(layer, B, H, W): [(dy, srcs) of every call]}: one weight-gradient launch per layer per step, when the arena is unpacked
+        # (None: frozen parameters, key None -- nothing will unpack)
+        self.pending = {} if key is not None else None
 
 
 class _ParamFn(torch.autograd.Function):
@@ -834,12 +809,10 @@ class _UpdateFn(torch.autograd.Function):
                                                head_out=None if slot is None else hb.head[slot],
                                                mslot=None if mt is None else (mb, mt),
                                                hlast_out=None if (slot is None or hb.hlast is None) else hb.hlast[slot])
-        if saved is not None and mt is not None:
-            saved["mb"] = (mb, mt)
-        if saved is not None and slot is not None:
-            saved["hb"] = (hb, slot)
-        if saved is not None and grad_samples is not None:
-            saved["gs"] = int(grad_samples)
+        if saved is not None:
+            saved.mb = (mb, mt) if mt is not None else None
+            saved.hb = (hb, slot) if slot is not None else None
+            saved.gs = int(grad_samples) if grad_samples is not None else None
         ctx.engine, ctx.st, ctx.saved = engine, st, saved
         ctx.ast, ctx.cst = ast, cst
         ctx.P = engine._packed(params) if need else None
@@ -957,9 +930,8 @@ class MotionBatch:
 
         def v(t):
             return None if t is None else t[:n].view(n * B, H, W, t.shape[-1])
-        S = dict(B=n * B, H=H, W=W, corr=v(self.corr), cor1=v(self.cor1), corflo=v(self.corflo), cols=v(self.cols), flo1=v(self.flo1),
-                 motion=v(self.motion), dcorr_out=v(self.dcorr))
-        eng.backward(S, P, st, None, None, None, need_input_grads=True, need_dflow=False, motion_only=v(self.dmotion))
+        A = _Saved(corr=v(self.corr), cor1=v(self.cor1), corflo=v(self.corflo), cols=v(self.cols), flo1=v(self.flo1), motion=v(self.motion))
+        eng.bwd_motion(_Bwd(eng, P, st, n * B, H, W, A.corr.device), A, v(self.dmotion), v(self.dcorr), False)
 
 
 def _one_tensor(ts):
@@ -994,9 +966,9 @@ class _MaskUpFn(torch.autograd.Function):
         head = hb.head[:T].view(T * B, H, W, 2 * eng.head_c)
         fl = torch.stack([f.float() for f in flows]).view(T * B, 2, H, W)
         mask = torch.empty(T * B, H, W, 576, device=head.device, dtype=torch.float32)
-        l = eng.layers["m2"]
-        ops.conv_forward([V(head, eng.head_c, eng.head_c)], P["m2"][0], P["m2"][2], T * B, H, W, l.kh, l.kw, 576, [Dst.nhwc(mask)],
-                         alpha=0.25, wpk_split=P["m2"][5])
+        l, p = eng.layers["m2"], P["m2"]
+        ops.conv_forward([V(head, eng.head_c, eng.head_c)], p.fwd, p.bias, T * B, H, W, l.kh, l.kw, 576, [Dst.nhwc(mask)],
+                         alpha=0.25, wpk_split=p.fwd_split)
         up = ops.upsample_fwd(fl, mask)
         ctx.hb, ctx.P = hb, P
         ctx.save_for_backward(fl, mask)
@@ -1025,24 +997,20 @@ class _MaskUpFn(torch.autograd.Function):
         # y = 0.25 * (W x + b): the data gradient applies the factor in its epilogue, the weight / bias gradients once per step
         # when the arena is unpacked (unpack_param_grads)
         gv, xv = V(dmask, 576), V(head, hc, hc)
-        if st is not None and st.key is not None:
-            dW, dB = eng._grad_arena(st, P, head.device)
-            if st.pending is not None:
-                st.pending.setdefault(("m2", T * B, H, W), []).append((gv, [xv]))
-            else:
-                ops.conv_wgrad(gv, [xv], dW["m2"], T * B, H, W, 1, 1, dbias=dB["m2"])
-        ops.conv_forward([gv], P["m2"][1], None, T * B, H, W, 1, 1, hc, [Dst.nhwc(dhead, hc).masked(xv)], alpha=0.25,
-                         wpk_split=P["m2"][6])
+        c = _Bwd(eng, P, st, T * B, H, W, head.device) if st is not None and st.key is not None else None
+        if c is not None:
+            c.wgrad("m2", gv, [xv])
+        ops.conv_forward([gv], P["m2"].dgrad, None, T * B, H, W, 1, 1, hc, [Dst.nhwc(dhead, hc).masked(xv)], alpha=0.25,
+                         wpk_split=P["m2"].dgrad_split)
         dfl = dflow.view(T, B, 2, H, W)
-        if HEADS_BWD_BATCH and hb.hlast is not None and st is not None and st.key is not None:
+        if HEADS_BWD_BATCH and hb.hlast is not None and c is not None:
             # the rest of the heads' backward depends on nothing but what this node just produced: the flow head (from dflow), then
             # the 3x3 convolution under both heads -- for all iterations at once; each iteration's backward starts from its slot
             # of dh_heads
             hb.dflow = dfl
             hb.dh_heads = torch.empty_like(hb.hlast)
-            Sb = dict(B=T * B, H=H, W=W, corr=head, head=head, hlast=hb.hlast[:T].view(T * B, H, W, hb.hlast.shape[-1]), dhead=dhead,
-                      dh_out=hb.dh_heads[:T].view(T * B, H, W, hb.hlast.shape[-1]))
-            eng.backward(Sb, P, st, None, None, dflow, need_input_grads=False, need_dflow=False, heads_only=True)
+            hl = hb.hlast.shape[-1]
+            eng.bwd_heads(c, head, hb.hlast[:T].view(T * B, H, W, hl), dhead, dflow, None, hb.dh_heads[:T].view(T * B, H, W, hl))
             hb.heads_done = True
         return (None, None) + tuple(dfl[t] for t in range(T))
 

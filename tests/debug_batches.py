@@ -18,7 +18,8 @@ dev = "cuda"
 
 
 def grads(model_fn, call, on, sup_k=None):
-    U.HEAD_BATCH = U.MOTION_BATCH = U.HEADS_BWD_BATCH = on
+    """on: one value for the three batches, or (HEAD_BATCH, MOTION_BATCH, HEADS_BWD_BATCH)."""
+    U.HEAD_BATCH, U.MOTION_BATCH, U.HEADS_BWD_BATCH = (bool(f) for f in on) if isinstance(on, tuple) else (on,) * 3
     torch.manual_seed(7)
     m = model_fn().to(dev).train()
     m.freeze_bn()
@@ -31,10 +32,11 @@ def grads(model_fn, call, on, sup_k=None):
     return [p.detach().clone() for p in preds], {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None}
 
 
-def compare(name, model_fn, call, sup_k=None, ref_call=None):
+def compare(name, model_fn, call, sup_k=None, ref_call=None, flags=True):
+    """flags: what the first run sets (see grads); the second run always has all three off."""
     was = (U.HEAD_BATCH, U.MOTION_BATCH, U.HEADS_BWD_BATCH)
     try:
-        pa, ga = grads(model_fn, call, True, sup_k)
+        pa, ga = grads(model_fn, call, flags, sup_k)
         pb, gb = grads(model_fn, ref_call or call, False, sup_k)
     finally:
         U.HEAD_BATCH, U.MOTION_BATCH, U.HEADS_BWD_BATCH = was

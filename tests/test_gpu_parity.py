@@ -919,6 +919,24 @@ def test_per_step_batches_against_the_per_iteration_path_on_odd_shapes(case):
                              ref_call=lambda m: m(i1, i2, c1, c2, ox, oy, iters=5))
 
 
+@pytest.mark.parametrize("flags", [(1, 1, 0), (1, 0, 1), (0, 1, 0), (1, 0, 0)], ids=lambda f: "head%d_motion%d_headsbwd%d" % f)
+def test_each_per_step_batch_alone_against_the_per_iteration_path(flags):
+    """The test above switches HEAD_BATCH, MOTION_BATCH and HEADS_BWD_BATCH together; every stage of the update block's backward
+    also has to compose with its neighbours' other route: the HeadBatch with per-iteration heads backward ((1,1,0), (1,0,0)), the
+    batched heads backward with a per-iteration motion encoder (1,0,1), the MotionBatch under per-iteration heads (0,1,0).  Same
+    case (B=3, 9x13 grid, two iterations) and same limits as there, each against all three off."""
+    import debug_batches as D
+    from flow_supervisor_amd.core import update as U
+    from flow_supervisor_amd.core.raft import RAFT
+    was = (U.HEAD_BATCH, U.MOTION_BATCH, U.HEADS_BWD_BATCH)
+    torch.manual_seed(123)
+    im1, im2 = torch.rand(3, 3, 72, 104, device=DEV) * 255, torch.rand(3, 3, 72, 104, device=DEV) * 255
+    try:
+        assert D.compare("raft_b3_iters2 %s" % (flags,), lambda: RAFT(D.ns()), lambda m: m(im1, im2, iters=2), flags=flags)
+    finally:
+        U.HEAD_BATCH, U.MOTION_BATCH, U.HEADS_BWD_BATCH = was
+
+
 @pytest.mark.parametrize("alt", [False, True])
 def test_eager_train_steps_leave_no_garbage_for_the_cyclic_collector(alt):
     """Device memory allocated after an eager train step must not depend on how many steps ran, WITHOUT the cyclic garbage
@@ -1711,6 +1729,36 @@ def test_update_block_odd_shapes_vs_oracle(B, H, W, precision):
         # split mode: with only ~200 pixels one ReLU that flips at a near-zero pre-activation moves a weight gradient by
         # a few 1e-3 of its norm (see test_update_block_vs_reference)
         assert rel <= (2e-4 if precision == "exact" else 1e-2), (k, rel)
+
+
+def test_update_block_frozen_parameters_vs_oracle(precision):
+    """The case (3, 7, 9) of the test above with requires_grad_(False) on every parameter of the block: the state behind such a
+    call has no key and nothing unpacks its arena (update._ParamState(None)).  Outputs and the four input gradients against the
+    CPU oracle within that test's limits; no parameter receives a gradient."""
+    from flow_supervisor_amd.core.update import BasicUpdateBlock
+    f = 1.0 if precision == "exact" else 8.0
+    B, H, W = 3, 7, 9
+    seed = 900 + H
+    blk = BasicUpdateBlock(ns(False), hidden_dim=128)
+    sd = procedural_state_dict(shapes("update_basic"), seed)
+    blk.load_state_dict(sd)
+    blk = blk.to(DEV)
+    for p in blk.parameters():
+        p.requires_grad_(False)
+    mk = lambda shp, s, sc=1.0: rand_tensor(shp, s, sc)
+    net_c = torch.tanh(mk((B, 128, H, W), seed + 1)); inp_c = torch.relu(mk((B, 128, H, W), seed + 2))
+    corr_c = mk((B, 324, H, W), seed + 3, 2.0); flow_c = mk((B, 2, H, W), seed + 4, 3.0)
+    ins_c = [t.clone().requires_grad_(True) for t in (net_c, inp_c, corr_c, flow_c)]
+    n_r, m_r, d_r = O.basic_update_block(sd, "", *ins_c)
+    wn, wm, wd = mk(tuple(n_r.shape), seed + 5), mk(tuple(m_r.shape), seed + 6), mk(tuple(d_r.shape), seed + 7)
+    ((n_r * wn).sum() + (m_r * wm).sum() + (d_r * wd).sum()).backward()
+    ins_g = [t.to(DEV).requires_grad_(True) for t in (net_c, inp_c, corr_c, flow_c)]
+    n_g, m_g, d_g = blk(*ins_g)
+    ((n_g * wn.to(DEV)).sum() + (m_g * wm.to(DEV)).sum() + (d_g * wd.to(DEV)).sum()).backward()
+    close(n_g, n_r, 2e-5 * f, what="net"); close(m_g, m_r, 2e-5 * f, what="mask"); close(d_g, d_r, 2e-5 * f, what="delta")
+    for a, b, nm in zip(ins_g, ins_c, ("dnet", "dinp", "dcorr", "dflow")):
+        close(a.grad, b.grad, 3e-4 * f, what=nm)
+    assert all(p.grad is None for p in blk.parameters())
 
 
 def test_lookup_far_out_of_range_and_zero_volume():

@@ -1,8 +1,20 @@
-"""Feature / context encoders.  These are callers of the hot path, kept as PyTorch-ROCm
-convolutions on purpose (BASELINE.json north_star); only the module/parameter names of
-pytorch/core/extractor.py are reproduced so reference checkpoints load (state_dict keys
-``conv1``, ``norm1``, ``layer{1,2,3}.{0,1}.conv{1,2,3}``, ``...downsample.{0,1}``, ``conv2``).
+"""Feature / context encoders.  Module and parameter names are those of pytorch/core/extractor.py, so reference
+checkpoints load (state_dict keys ``conv1``, ``norm1``, ``layer{1,2,3}.{0,1}.conv{1,2,3}``, ``...downsample.{0,1}``,
+``conv2``).  What runs where, for an fp32 CUDA input outside autocast whose norms are non-affine InstanceNorm or BatchNorm on
+running statistics (_norm_kind):
+  * the 7x7 stride-2 stem on csrc/stem.hip (_StemFn), channels_last from there on;
+  * stride-1 1x1 / 3x3 convolutions on the implicit-GEMM kernels (_ConvCL), from weight images packed once per parameter
+    version (_prepare_packs);
+  * the two strided convolutions of a stride-2 residual unit on the same kernels over a space-to-depth input (_StridedPairFn);
+  * norm + ReLU (+ the unit's add and outer ReLU) on csrc/norm_cl.hip (_InstNormReluCL, _FrozenBNReluCL).
+MIOpen, on NCHW tensors behind a layout copy, is what these do not cover: stride-2 units at odd sizes, channel counts that are
+no multiple of four, the stem at other shapes.  Other norms (GroupNorm, training-mode BatchNorm, none), autocast and CPU
+tensors run the framework's modules throughout, as does FSRAFT_ENCODER_CL=0 with the norm + ReLU on the NCHW kernels of
+csrc/norm.hip.  The switches STATS_IN_EPILOGUE, STEM_KERNEL, S2D_UNITS and S2D_EMIT turn single routes off.
 """
+import os
+from collections import namedtuple
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -16,27 +28,16 @@ class _InstNormRelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, eps, relu):
-        from .. import _lib as L
         x = x.contiguous()
-        N, C, H, W = x.shape
-        y = torch.empty_like(x)
-        stats = torch.empty(N * C, 2, device=x.device, dtype=torch.float32)
-        L.check(L.load().fsraft_inorm_relu_fwd(L.ptr(x), L.ptr(y), L.ptr(stats), N * C, H * W, float(eps), int(relu),
-                                               L.stream()), "inorm_relu_fwd")
+        y, stats = ops.inorm_relu_fwd(x, eps, relu)
         ctx.save_for_backward(x, stats)
         ctx.relu = relu
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib as L
         x, stats = ctx.saved_tensors
-        N, C, H, W = x.shape
-        g = g.contiguous()
-        dx = torch.empty_like(x)
-        L.check(L.load().fsraft_inorm_relu_bwd(L.ptr(g), L.ptr(x), L.ptr(stats), L.ptr(dx), N * C, H * W, int(ctx.relu),
-                                               L.stream()), "inorm_relu_bwd")
-        return dx, None, None
+        return ops.inorm_relu_bwd(g.contiguous(), x, stats, ctx.relu), None, None
 
 
 class _FrozenBNRelu(torch.autograd.Function):
@@ -47,16 +48,12 @@ class _FrozenBNRelu(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cbias, weight, bias, rm, rv, eps, relu):
-        from .. import _lib as L
         x = x.contiguous()
-        N, C, H, W = x.shape
         rs = torch.rsqrt(rv.float() + eps)
         scale = (weight.float() * rs).contiguous()
         rmc = rm.float() - cbias.float() if cbias is not None else rm.float()       # effective mean seen by x
         shift = (bias.float() - rmc * scale).contiguous()
-        y = torch.empty_like(x)
-        L.check(L.load().fsraft_affine_relu_fwd(L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(y), N * C, C, H * W, int(relu),
-                                                L.stream()), "affine_relu_fwd")
+        y = ops.affine_relu_fwd(x, scale, shift, relu)
         ctx.save_for_backward(x, scale, shift, rs, rmc)
         ctx.relu = relu
         ctx.has_cbias = cbias is not None
@@ -64,14 +61,8 @@ class _FrozenBNRelu(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib as L
         x, scale, shift, rs, rm = ctx.saved_tensors
-        N, C, H, W = x.shape
-        g = g.contiguous()
-        dx = torch.empty_like(x)
-        sums = ops.zeros(2, C, device=x.device)
-        L.check(L.load().fsraft_affine_relu_bwd(L.ptr(g), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(dx), L.ptr(sums[0]),
-                                                L.ptr(sums[1]), N * C, C, H * W, int(ctx.relu), L.stream()), "affine_relu_bwd")
+        dx, sums = ops.affine_relu_bwd(g.contiguous(), x, scale, shift, ctx.relu)
         dweight = rs * (sums[1] - rm * sums[0])               # sum g' * (x + cbias - rm) * rs
         dcbias = scale * sums[0] if ctx.has_cbias else None   # = sum over pixels of dx
         return dx, dcbias, dweight, sums[0], None, None, None, None
@@ -81,8 +72,9 @@ def _is_cl(x):
     return x.dim() == 4 and x.shape[1] > 1 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
 
 
-def _cl_norm_ok(x):
-    return x.shape[1] % 4 == 0 and 4 <= x.shape[1] <= 256
+def _cl_channels_ok(C):
+    """Channel counts the channels_last norm kernels (csrc/norm_cl.hip) take."""
+    return C % 4 == 0 and 4 <= C <= 256
 
 
 def _fast(x):
@@ -95,7 +87,6 @@ def _as_cl(x):
     if _is_cl(x):
         return x
     if _fast(x) and x.is_contiguous():
-        from .. import ops
         B, C, H, W = x.shape
         return ops.nchw_to_nhwc(x, torch.empty(B, H, W, C, device=x.device, dtype=torch.float32)).permute(0, 3, 1, 2)
     return x.contiguous(memory_format=torch.channels_last)
@@ -105,7 +96,6 @@ def _as_nchw(x):
     if x.is_contiguous():
         return x
     if _fast(x) and _is_cl(x):
-        from .. import ops
         return ops.nhwc_to_nchw(x.permute(0, 2, 3, 1))
     return x.contiguous()
 
@@ -141,50 +131,42 @@ class _ResLink:
         self.armed = False
 
 
+def _cl_norm_enter(ctx, x, res, link, s2d):
+    """Start of the forward of both channels_last norm Functions -> (x, res) channels_last.  s2d: the result leaves in the
+    space-to-depth layout of the stride-2 unit that consumes it -- a [N, 4C, H/2, W/2] channels_last tensor -- and the
+    gradient comes back in it (see _S2D; ctx.s2w is the `s2w` of the ops wrappers)."""
+    ctx.in_cl = _is_cl(x)
+    ctx.link = link
+    x = _as_cl(x)
+    ctx.s2w = x.shape[3] if s2d else 0
+    return x, (_as_cl(res) if res is not None else None)
+
+
+def _cl_norm_leave(ctx, dx, dres):
+    """End of their backward -> (x's gradient, the shortcut's gradient as autograd gets it)."""
+    if ctx.link is not None and ctx.link.armed:
+        dres, ctx.link.dres = None, dres      # the shortcut's gradient travels through the link: conv1's backward returns the sum
+    return dx if ctx.in_cl else _as_nchw(dx), dres      # an NCHW producer (MIOpen) gets an NCHW gradient
+
+
 class _InstNormReluCL(torch.autograd.Function):
     """_InstNormRelu for channels_last tensors (storage [N][H*W][C]): csrc/norm_cl.hip.  With `res` (the shortcut of a
     residual unit, channels_last) the result is relu(res + relu?(norm(x))) in the same pass -- the unit's add and final ReLU
-    (and their backward) cost no extra trip over the tensor."""
+    (and their backward) cost no extra trip over the tensor.  `sums`: the _NormSums of the convolution that produced x."""
 
     @staticmethod
     def forward(ctx, x, eps, relu, res=None, link=None, sums=None, s2d=False):
-        from .. import _lib as L
-        ctx.in_cl = _is_cl(x)
-        ctx.link = link
-        x = _as_cl(x)
-        N, C, H, W = x.shape
-        if res is not None:
-            res = _as_cl(res)
-        # s2d: the result leaves in the space-to-depth layout of the stride-2 unit that consumes it -- a [N, 4C, H/2, W/2]
-        # channels_last tensor -- and the gradient comes back in it (see _emit_s2d)
-        ctx.s2w = W if s2d else 0
-        y = (torch.empty(N, H // 2, W // 2, 4 * C, device=x.device, dtype=torch.float32).permute(0, 3, 1, 2) if s2d
-             else torch.empty_like(x))                            # preserves channels_last
-        # partial rows (norm_cl.hip) -- already filled when the convolution that produced x carried the sums in its epilogue
-        have = sums is not None and sums.acc is not None and tuple(sums.acc.shape) == (2, N * 8, C)
-        acc = sums.acc if have else ops.zeros(2, N * 8, C, device=x.device)
-        stats = torch.empty(N, C, 2, device=x.device, dtype=torch.float32)
-        L.check(L.load().fsraft_inorm_relu_cl_fwd(L.ptr(x), L.ptr(res), L.ptr(y), L.ptr(acc[0]), L.ptr(acc[1]), L.ptr(stats), N, H * W,
-                                                  C, float(eps), int(relu), int(have), ctx.s2w, L.stream()), "inorm_relu_cl_fwd")
-        ctx.fused = res is not None
-        ctx.save_for_backward(x, stats, y if ctx.fused else None)
+        x, res = _cl_norm_enter(ctx, x, res, link, s2d)
+        y, stats = ops.inorm_relu_cl_fwd(x, res, eps, relu, sums.acc if sums is not None else None, ctx.s2w)
+        ctx.save_for_backward(x, stats, y if res is not None else None)
         ctx.relu = relu
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib as L
         x, stats, out = ctx.saved_tensors
-        N, C, H, W = x.shape
-        g = _as_cl(g)
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if ctx.fused else None
-        acc = ops.zeros(2, N * 8, C, device=x.device)      # partial rows (norm_cl.hip)
-        L.check(L.load().fsraft_inorm_relu_cl_bwd(L.ptr(g), L.ptr(x), L.ptr(stats), L.ptr(out), L.ptr(acc[0]), L.ptr(acc[1]), L.ptr(dx),
-                                                  L.ptr(dres), N, H * W, C, int(ctx.relu), ctx.s2w, L.stream()), "inorm_relu_cl_bwd")
-        if ctx.link is not None and ctx.link.armed:
-            ctx.link.dres, dres = dres, None      # the shortcut's gradient travels through the link: conv1's backward returns the sum
-        return dx if ctx.in_cl else _as_nchw(dx), None, None, dres, None, None, None     # an NCHW producer (MIOpen) gets an NCHW gradient
+        dx, dres = _cl_norm_leave(ctx, *ops.inorm_relu_cl_bwd(_as_cl(g), x, stats, out, ctx.relu, ctx.s2w))
+        return dx, None, None, dres, None, None, None
 
 
 class _FrozenBNReluCL(torch.autograd.Function):
@@ -192,132 +174,119 @@ class _FrozenBNReluCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, cbias, weight, bias, rm, rv, eps, relu, res=None, link=None, s2d=False):
-        from .. import _lib as L
-        ctx.in_cl = _is_cl(x)
-        ctx.link = link
-        x = _as_cl(x)
-        N, C, H, W = x.shape
-        ctx.s2w = W if s2d else 0                     # (as in _InstNormReluCL)
-        if res is not None:
-            res = _as_cl(res)
-        fold = torch.empty(4, C, device=x.device, dtype=torch.float32)       # scale, shift, rs, rmc: one launch (csrc/norm_cl.hip)
-        scale, shift, rs, rmc = fold[0], fold[1], fold[2], fold[3]
-        L.check(L.load().fsraft_bn_fold(L.ptr(weight.detach().float().contiguous()), L.ptr(bias.detach().float().contiguous()),
-                                        L.ptr(rm.float().contiguous()), L.ptr(rv.float().contiguous()),
-                                        L.ptr(cbias.detach().float().contiguous()) if cbias is not None else None, float(eps), C,
-                                        L.ptr(scale), L.ptr(shift), L.ptr(rs), L.ptr(rmc), L.stream()), "bn_fold")
-        y = torch.empty(N, H // 2, W // 2, 4 * C, device=x.device, dtype=torch.float32).permute(0, 3, 1, 2) if s2d else torch.empty_like(x)
-        L.check(L.load().fsraft_affine_relu_cl_fwd(L.ptr(x), L.ptr(res), L.ptr(scale), L.ptr(shift), L.ptr(y), N * H * W, C, int(relu),
-                                                   H * W, ctx.s2w, L.stream()), "affine_relu_cl_fwd")
-        ctx.fused = res is not None
-        ctx.save_for_backward(x, scale, shift, rs, rmc, y if ctx.fused else None)
+        x, res = _cl_norm_enter(ctx, x, res, link, s2d)
+        scale, shift, rs, rmc = ops.bn_fold(weight, bias, rm, rv, cbias, eps)
+        y = ops.affine_relu_cl_fwd(x, res, scale, shift, relu, ctx.s2w)
+        ctx.save_for_backward(x, scale, shift, rs, rmc, y if res is not None else None)
         ctx.relu = relu
         ctx.has_cbias = cbias is not None
         return y
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib as L
-        x, scale, shift, rs, rm, out = ctx.saved_tensors
-        N, C, H, W = x.shape
-        g = _as_cl(g)
-        dx = torch.empty_like(x)
-        dres = torch.empty_like(x) if ctx.fused else None
-        part = ops.zeros(2, N * 8, C, device=x.device)      # partial rows (see norm_cl.hip)
-        L.check(L.load().fsraft_affine_relu_cl_bwd(L.ptr(g), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(out), L.ptr(dx), L.ptr(dres),
-                                                   L.ptr(part[0]), L.ptr(part[1]), N, H * W, C, int(ctx.relu), ctx.s2w, L.stream()),
-                "affine_relu_cl_bwd")
-        dpar = torch.empty(3, C, device=x.device, dtype=torch.float32)       # dweight, dbias, dcbias: one launch
-        L.check(L.load().fsraft_bn_fold_bwd(L.ptr(part), N * 8, C, L.ptr(rs), L.ptr(rm), L.ptr(scale), L.ptr(dpar[0]), L.ptr(dpar[1]),
-                                            L.ptr(dpar[2]) if ctx.has_cbias else None, L.stream()), "bn_fold_bwd")
-        if ctx.link is not None and ctx.link.armed:
-            ctx.link.dres, dres = dres, None      # (see _ResLink)
-        return (dx if ctx.in_cl else _as_nchw(dx), dpar[2] if ctx.has_cbias else None, dpar[0], dpar[1], None, None, None, None, dres,
-                None, None)
+        x, scale, shift, rs, rmc, out = ctx.saved_tensors
+        dx, dres, part = ops.affine_relu_cl_bwd(_as_cl(g), x, scale, shift, out, ctx.relu, ctx.s2w)
+        dweight, dbias, dcbias = ops.bn_fold_bwd(part, rs, rmc, scale, ctx.has_cbias)
+        dx, dres = _cl_norm_leave(ctx, dx, dres)
+        return dx, dcbias, dweight, dbias, None, None, None, None, dres, None, None
+
+
+# GEMM-ready images of one weight (ops.pack_weight modes): fwd = mode 0 and dgrad = mode 1 in fp32, *_split = modes 10 / 11 for
+# the split-bf16 kernels.  An fp32 image no kernel will read is not built: the field then holds the split image itself.
+_GemmPacks = namedtuple("_GemmPacks", "fwd fwd_split dgrad dgrad_split")
+# ... of a stride-1 1x1 / 3x3 convolution, cached as module.__dict__["_fs_packs"]; *_frag = the split images in fragment order
+# (ops.fragment_order) for the resident-patch kernel: 3x3 with 33..64 channels on the GEMM's k side, else None
+_ConvPacks = namedtuple("_ConvPacks", "key fwd fwd_split dgrad dgrad_split fwd_frag dgrad_frag")
+# ... of a stride-2 unit, cached as block.__dict__["_fs_pair_packs"]: conv3 = its 3x3 stride-2 convolution as the 2x2 stride-1
+# one over the space-to-depth input (_s2d_weight), shortcut = its 1x1; a _GemmPacks each
+_PairPacks = namedtuple("_PairPacks", "key conv3 shortcut")
 
 
 def _conv_key(conv):
-    from .. import ops
     w = conv.weight
     return (w.data_ptr(), w._version, ops.exact_mode())
 
 
-def _queue_conv_packs(plan, conv):
-    """Queue the packed forward / data-gradient matrices of a stride-1 1x1 / 3x3 convolution; returns the handle tuple that
-    _finish_conv_packs turns into the cached `(key, fwd fp32, fwd split, dgrad fp32, dgrad split, fwd fragment order, dgrad
-    fragment order)`.  The fragment-order packs are the resident-patch kernel's (33..64 input channels, 3x3)."""
-    from .. import ops
+def _pair_key(block):
+    w3, wsc = block.conv1.weight, block.downsample[0].weight
+    return (w3.data_ptr(), w3._version, wsc.data_ptr(), wsc._version, ops.exact_mode())
+
+
+def _queue_gemm_packs(plan, w, cin, order, **how):
+    """Queue the images of weight `w` seen as [Cout, cin, ...] (`how`: PackPlan.pack's cin_full / s2d) -> a _GemmPacks of plan
+    handles.  The fp32 images are built in exact arithmetic and for a side of at most 32 rows, which stays on the fp32
+    kernels.  `order`: the modes in the order their jobs enter the plan, which is the layout of the packed buffer."""
+    exact = ops.exact_mode()
+    want = {10: True, 11: True, 0: exact or w.shape[0] <= 32, 1: exact or cin <= 32}
+    h = {mode: plan.pack([w], [cin], mode, **how) for mode in order if want[mode]}
+    return _GemmPacks(h.get(0, h[10]), h[10], h.get(1, h[11]), h[11])
+
+
+def _queue_conv_packs(plan, conv, key):
+    """The _ConvPacks of a stride-1 1x1 / 3x3 convolution, as plan handles."""
     wd = conv.weight.detach()
     N, C, KH, KW = wd.shape
-    exact = ops.exact_mode()
-    fs = plan.pack([wd], [C], 10)
-    f = plan.pack([wd], [C], 0) if (exact or N <= 32) else fs
-    ds = plan.pack([wd], [C], 11)
-    d = plan.pack([wd], [C], 1) if (exact or C <= 32) else ds
+    g = _queue_gemm_packs(plan, wd, C, (10, 0, 11, 1))
     ff = plan.pack([wd], [C], 10, frag=True) if (KH, KW) == (3, 3) and 32 < C <= 64 else None
     df = plan.pack([wd], [C], 11, frag=True) if (KH, KW) == (3, 3) and 32 < N <= 64 else None
-    return (f, fs, d, ds, ff, df)
+    return _ConvPacks(key, *g, ff, df)
+
+
+def _queue_pair_packs(plan, block, key):
+    """The _PairPacks of a stride-2 unit, as plan handles."""
+    w3, ws = block.conv1.weight.detach(), block.downsample[0].weight.detach()
+    C = w3.shape[1]
+    # the 3x3 stride-2 weight seen as its 2x2 stride-1 equivalent over the space-to-depth input (flag s2d): [N][4C][2][2]
+    return _PairPacks(key, _queue_gemm_packs(plan, w3, 4 * C, (10, 11, 0, 1), cin_full=C, s2d=True),
+                      _queue_gemm_packs(plan, ws, ws.shape[1], (10, 11, 0, 1)))
+
+
+def _packed(h, out):
+    """A record of plan handles -> the same record of the packed tensors `out` (PackPlan.run)."""
+    if isinstance(h, _PairPacks):
+        return h._replace(conv3=_packed(h.conv3, out), shortcut=_packed(h.shortcut, out))
+    return h._replace(**{f: out[v] for f, v in zip(h._fields, h) if isinstance(v, int)})      # (not the key, not None)
+
+
+def _stale(module, slot, key):
+    c = module.__dict__.get(slot)
+    return c is None or c.key != key
 
 
 def _prepare_packs(root):
     """Every packed weight image of an encoder (or of one convolution) whose parameter changed since it was packed, built by
     ONE batched launch per 16 matrices (fsraft_pack_conv_weights) instead of two to four launches per layer plus the torch
     ops of the space-to-depth rewrite and of the fragment-order permutation."""
-    from .. import ops
-    todo = []
+    todo = []       # (cache slot, module, key), in module order
     for m in root.modules():
-        if isinstance(m, _Block) and _pair_shape_ok(m):
-            w3, wsc = m.conv1.weight, m.downsample[0].weight
-            key = (w3.data_ptr(), w3._version, wsc.data_ptr(), wsc._version, ops.exact_mode())
-            c = m.__dict__.get("_fs_pair_packs")
-            if (c is None or c[0] != key) and w3.is_cuda and w3.dtype == torch.float32:
-                todo.append(("pair", m, key))
+        if isinstance(m, _Block) and _pair_structure_ok(m):
+            w3 = m.conv1.weight
+            key = _pair_key(m)
+            if _stale(m, "_fs_pair_packs", key) and w3.is_cuda and w3.dtype == torch.float32:
+                todo.append(("_fs_pair_packs", m, key))
         if (isinstance(m, nn.Conv2d) and m.stride == (1, 1) and m.kernel_size in ((1, 1), (3, 3)) and m.groups == 1
                 and m.weight.is_cuda and m.weight.dtype == torch.float32):
-            c = m.__dict__.get("_fs_packs")
             key = _conv_key(m)
-            if c is None or c[0] != key:
-                todo.append(("conv", m, key))
+            if _stale(m, "_fs_packs", key):
+                todo.append(("_fs_packs", m, key))
     if not todo:
         return
     with torch.no_grad():
-        plan = ops.PackPlan(todo[0][1].conv1.weight.device if todo[0][0] == "pair" else todo[0][1].weight.device)
-        hs = []
-        exact = ops.exact_mode()
-        for kind, m, key in todo:
-            if kind == "conv":
-                hs.append(_queue_conv_packs(plan, m))
-                continue
-            w3, ws = m.conv1.weight.detach(), m.downsample[0].weight.detach()
-            N, C = w3.shape[:2]
-            # the 3x3 stride-2 weight seen as its 2x2 stride-1 equivalent over the space-to-depth input (flag s2d): [N][4C][2][2]
-            a = plan.pack([w3], [4 * C], 10, cin_full=C, s2d=True)
-            b = plan.pack([w3], [4 * C], 11, cin_full=C, s2d=True)
-            a0 = plan.pack([w3], [4 * C], 0, cin_full=C, s2d=True) if (exact or N <= 32) else a
-            b0 = plan.pack([w3], [4 * C], 1, cin_full=C, s2d=True) if (exact or 4 * C <= 32) else b
-            Ns, Cs = ws.shape[:2]
-            c_ = plan.pack([ws], [Cs], 10)
-            d_ = plan.pack([ws], [Cs], 11)
-            c0 = plan.pack([ws], [Cs], 0) if (exact or Ns <= 32) else c_
-            d0 = plan.pack([ws], [Cs], 1) if (exact or Cs <= 32) else d_
-            hs.append(((a0, a, b0, b), (c0, c_, d0, d_)))
+        _, first, _ = todo[0]
+        plan = ops.PackPlan((first.conv1 if isinstance(first, _Block) else first).weight.device)
+        hs = [(_queue_pair_packs if slot == "_fs_pair_packs" else _queue_conv_packs)(plan, m, key) for slot, m, key in todo]
         out = plan.run()
-        for (kind, m, key), h in zip(todo, hs):
-            if kind == "conv":
-                m.__dict__["_fs_packs"] = (key,) + tuple(None if i is None else out[i] for i in h)
-            else:
-                m.__dict__["_fs_pair_packs"] = (key, tuple(out[i] for i in h[0]), tuple(out[i] for i in h[1]))
+        for (slot, m, key), h in zip(todo, hs):
+            m.__dict__[slot] = _packed(h, out)
 
 
 def _weight_packs(conv):
-    """Packed forward / data-gradient matrices of a convolution for the split-bf16 implicit GEMM, cached on the module and
-    rebuilt whenever the weight tensor changes (optimizer step, load_state_dict).  The encoders build all of theirs at once
-    (_prepare_packs at the top of forward); a convolution used on its own gets here with a stale cache and packs itself."""
-    c = conv.__dict__.get("_fs_packs")
-    if c is None or c[0] != _conv_key(conv):
+    """The _ConvPacks of a convolution, cached on the module and rebuilt whenever the weight tensor changes (optimizer step,
+    load_state_dict).  The encoders build all of theirs at once (_prepare_packs at the top of forward); a convolution used on
+    its own gets here with a stale cache and packs itself."""
+    if _stale(conv, "_fs_packs", _conv_key(conv)):
         _prepare_packs(conv)
-        c = conv.__dict__["_fs_packs"]
-    return c
+    return conv.__dict__["_fs_packs"]
 
 
 class _ConvCL(torch.autograd.Function):
@@ -328,7 +297,6 @@ class _ConvCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, packs, link=None, sums=None):
-        from .. import ops
         ctx.link = link if _is_cl(x) else None       # (a converted copy of x is not the tensor the shortcut gradient belongs to)
         if ctx.link is not None:
             ctx.link.armed = True                    # this node's backward will collect the parked shortcut gradient
@@ -338,9 +306,9 @@ class _ConvCL(torch.autograd.Function):
         out = torch.empty(B, H, W, N, device=x.device, dtype=torch.float32)
         # sums (a _NormSums holder): the InstanceNorm behind this convolution wants the per-image column sums of the result; the
         # kernel adds them up in its epilogue where it can, and the norm then skips its own statistics pass
-        acc = ops.zeros(2, B * 8, N, device=x.device) if (sums is not None and bias is None and STATS_IN_EPILOGUE) else None
-        carried = ops.conv_forward([ops.V(x.permute(0, 2, 3, 1), C)], packs[1], bias, B, H, W, KH, KW, N, [ops.Dst.nhwc(out)],
-                                   wpk_split=packs[2], wpk_frag=packs[5], stats=acc)
+        acc = ops.norm_partial_rows(B, N, x.device) if (sums is not None and bias is None and STATS_IN_EPILOGUE) else None
+        carried = ops.conv_forward([ops.V(x.permute(0, 2, 3, 1), C)], packs.fwd, bias, B, H, W, KH, KW, N, [ops.Dst.nhwc(out)],
+                                   wpk_split=packs.fwd_split, wpk_frag=packs.fwd_frag, stats=acc)
         if sums is not None:
             sums.acc = acc if carried else None
         ctx.save_for_backward(x, weight)
@@ -350,27 +318,27 @@ class _ConvCL(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import ops
         x, weight = ctx.saved_tensors
         B, C, H, W = x.shape
         N, _, KH, KW = weight.shape
         g = _as_cl(g)
         gv = ops.V(g.permute(0, 2, 3, 1), N)
+        p = ctx.packs
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dres = ctx.link.dres if ctx.link is not None else None
             if dres is not None and dres.shape == x.shape and _is_cl(dres) and dres.dtype == torch.float32:
                 # residual unit: this data gradient is added into the parked shortcut gradient, the sum is x's gradient (see _ResLink)
                 ctx.link.dres = None
-                ops.conv_forward([gv], ctx.packs[3], None, B, H, W, KH, KW, C, [ops.Dst.nhwc(dres.permute(0, 2, 3, 1), acc=True)],
-                                 wpk_split=ctx.packs[4], wpk_frag=ctx.packs[6])
+                ops.conv_forward([gv], p.dgrad, None, B, H, W, KH, KW, C, [ops.Dst.nhwc(dres.permute(0, 2, 3, 1), acc=True)],
+                                 wpk_split=p.dgrad_split, wpk_frag=p.dgrad_frag)
                 dx = dres
             else:
                 if dres is not None:          # (a parked gradient this route cannot add into: hand both over, the sum is made here)
                     ctx.link.dres = None
                 dxb = torch.empty(B, H, W, C, device=x.device, dtype=torch.float32)
-                ops.conv_forward([gv], ctx.packs[3], None, B, H, W, KH, KW, C, [ops.Dst.nhwc(dxb)], wpk_split=ctx.packs[4],
-                                 wpk_frag=ctx.packs[6])
+                ops.conv_forward([gv], p.dgrad, None, B, H, W, KH, KW, C, [ops.Dst.nhwc(dxb)], wpk_split=p.dgrad_split,
+                                 wpk_frag=p.dgrad_frag)
                 dx = dxb.permute(0, 3, 1, 2)
                 if dres is not None:
                     dx = dx + dres
@@ -391,20 +359,17 @@ class _StemFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        from .. import ops
         x = x.contiguous()
         ctx.save_for_backward(x)
         return ops.stem_fwd(x, w.detach()).permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, g):
-        from .. import ops
         (x,) = ctx.saved_tensors
         return None, ops.stem_wgrad(x, _as_cl(g).permute(0, 2, 3, 1))
 
 
 def _stem_ok(conv, x):
-    import os
     return (STEM_KERNEL and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros" and conv.in_channels == 3
             and conv.out_channels in (32, 64) and _fast(x) and not x.requires_grad and not torch.is_autocast_enabled()
@@ -417,7 +382,7 @@ S2D_UNITS = True           # False: the stride-2 units fall back to MIOpen behin
 
 
 class _NormSums:
-    """Hand-over between a convolution and the InstanceNorm behind it: `acc` = the [2, B * 8, C] partial rows of the
+    """Hand-over between a convolution and the InstanceNorm behind it: `acc` = the partial rows (ops.norm_partial_rows) of the
     result's column sums / sums of squares when the convolution's kernel accumulated them in its epilogue, else None."""
     __slots__ = ("acc",)
 
@@ -465,9 +430,9 @@ def _s2d_weight_grad(dw, C):
     return out
 
 
-def _pair_shape_ok(block):
+def _pair_structure_ok(block):
     """A unit whose first convolution is 3x3 / stride 2 / pad 1 with a 1x1 / stride 2 shortcut: the pair that runs on the
-    stride-1 kernels over a space-to-depth copy of the input."""
+    stride-1 kernels over a space-to-depth copy of the input.  (Module structure only: what _prepare_packs goes by.)"""
     c1 = getattr(block, "conv1", None)
     ds = block.downsample[0] if getattr(block, "downsample", None) is not None else None
     return (block.n == 2 and c1 is not None and ds is not None and c1.kernel_size == (3, 3) and c1.stride == (2, 2)
@@ -475,18 +440,20 @@ def _pair_shape_ok(block):
             and ds.stride == (2, 2) and ds.padding == (0, 0) and ds.groups == 1)
 
 
+def _pair_ok(block, C, H, W):
+    """Does `block` take the space-to-depth pair (_StridedPairFn) for a channels_last [B, C, H, W] input?  Even sizes, and
+    channel counts its kernels and the norm kernels behind them take."""
+    return (S2D_UNITS and _pair_structure_ok(block) and H % 2 == 0 and W % 2 == 0 and C % 4 == 0
+            and _cl_channels_ok(block.conv1.out_channels))
+
+
 def _pair_packs(block):
-    """Packed matrices of a stride-2 residual unit's first convolution (as 2x2 over space-to-depth: the rewrite
+    """The _PairPacks of a stride-2 residual unit: its first convolution as 2x2 over space-to-depth (the rewrite
     `input row 2y - 1 + k = 2(y + t - 1) + s` maps 3x3 tap k to (2x2 tap t, sub-pixel s), 7 of the 16 (tap, sub-pixel) slots
-    are structural zeros) and of its 1x1 shortcut: `(key, (fwd fp32, fwd split, dgrad fp32, dgrad split) x 2)`."""
-    from .. import ops
-    w3, wsc = block.conv1.weight, block.downsample[0].weight
-    key = (w3.data_ptr(), w3._version, wsc.data_ptr(), wsc._version, ops.exact_mode())
-    c = block.__dict__.get("_fs_pair_packs")
-    if c is None or c[0] != key:
+    are structural zeros) and its 1x1 shortcut; cached and rebuilt like _weight_packs."""
+    if _stale(block, "_fs_pair_packs", _pair_key(block)):
         _prepare_packs(block)
-        c = block.__dict__["_fs_pair_packs"]
-    return c
+    return block.__dict__["_fs_pair_packs"]
 
 
 class _StridedPairFn(torch.autograd.Function):
@@ -500,7 +467,6 @@ class _StridedPairFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w3, wsc, packs, pre=False):
-        from .. import ops
         x = _as_cl(x)
         ctx.pre = pre
         if pre:         # x already IS the space-to-depth tensor [B, 4C, H/2, W/2] (written by the norm before it: _S2D)
@@ -514,27 +480,26 @@ class _StridedPairFn(torch.autograd.Function):
         N, Ns = w3.shape[0], wsc.shape[0]
         y1 = torch.empty(B, h, w, N, device=x.device, dtype=torch.float32)
         ys = torch.empty(B, h, w, Ns, device=x.device, dtype=torch.float32)
-        p, q = packs[1], packs[2]
-        ops.conv_forward([ops.V(xs, 4 * C)], p[0], None, B, h, w, 2, 2, N, [ops.Dst.nhwc(y1)], wpk_split=p[1])
-        ops.conv_forward([ops.V(xs, C, 0)], q[0], None, B, h, w, 1, 1, Ns, [ops.Dst.nhwc(ys)], wpk_split=q[1])
+        p, q = packs.conv3, packs.shortcut
+        ops.conv_forward([ops.V(xs, 4 * C)], p.fwd, None, B, h, w, 2, 2, N, [ops.Dst.nhwc(y1)], wpk_split=p.fwd_split)
+        ops.conv_forward([ops.V(xs, C, 0)], q.fwd, None, B, h, w, 1, 1, Ns, [ops.Dst.nhwc(ys)], wpk_split=q.fwd_split)
         ctx.save_for_backward(xs, w3, wsc)
         ctx.packs = packs
         return y1.permute(0, 3, 1, 2), ys.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, g1, gs):
-        from .. import ops
         xs, w3, wsc = ctx.saved_tensors
         B, h, w, C4 = xs.shape
         C, N, Ns = C4 // 4, w3.shape[0], wsc.shape[0]
-        p, q = ctx.packs[1], ctx.packs[2]
+        p, q = ctx.packs.conv3, ctx.packs.shortcut
         g1v = ops.V(_as_cl(g1).permute(0, 2, 3, 1), N)
         gsv = ops.V(_as_cl(gs).permute(0, 2, 3, 1), Ns)
         dx = dw3 = dwsc = None
         if ctx.needs_input_grad[0]:
             dxs = torch.empty(B, h, w, C4, device=xs.device, dtype=torch.float32)
-            ops.conv_forward([g1v], p[2], None, B, h, w, 2, 2, C4, [ops.Dst.nhwc(dxs)], wpk_split=p[3], pad=(0, 0))
-            ops.conv_forward([gsv], q[2], None, B, h, w, 1, 1, C, [ops.Dst.nhwc(dxs, 0, 0, True)], wpk_split=q[3])
+            ops.conv_forward([g1v], p.dgrad, None, B, h, w, 2, 2, C4, [ops.Dst.nhwc(dxs)], wpk_split=p.dgrad_split, pad=(0, 0))
+            ops.conv_forward([gsv], q.dgrad, None, B, h, w, 1, 1, C, [ops.Dst.nhwc(dxs, 0, 0, True)], wpk_split=q.dgrad_split)
             dx = (dxs if ctx.pre else ops.space_to_depth2(dxs, inverse=True)).permute(0, 3, 1, 2)
         items = []
         if ctx.needs_input_grad[1]:
@@ -551,22 +516,36 @@ class _StridedPairFn(torch.autograd.Function):
         return dx, dw3, dwsc, None, None
 
 
-def _norm_act(norm, y, cbias, relu, res=None):
-    """relu?(norm(y + cbias)) (+ fused residual) for a channels_last convolution output and one of the two norm kinds the
-    channels_last path covers; cbias is the bias the convolution ran without."""
-    if isinstance(norm, nn.InstanceNorm2d):
-        return _InstNormReluCL.apply(y, norm.eps, relu, res)
-    return _FrozenBNReluCL.apply(y, cbias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps, relu, res)
+def _norm_kind(norm):
+    """Which fsraft norm + ReLU kernels cover `norm`: "instance" (InstanceNorm2d without affine parameters or running
+    statistics), "frozen_bn" (affine BatchNorm2d using its running statistics: eval mode / freeze_bn), or None."""
+    if isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats:
+        return "instance"
+    if isinstance(norm, nn.BatchNorm2d) and not norm.training and norm.track_running_stats and norm.affine:
+        return "frozen_bn"
+    return None
 
 
-def _pair_ok_shape(block, C, H, W):
-    import os
-    return (S2D_UNITS and _pair_shape_ok(block) and H % 2 == 0
-            and W % 2 == 0 and C % 4 == 0 and _cl_norm_ok(torch.empty(0, block.conv1.out_channels)))
-
-
-def _pair_ok(block, x):
-    return _pair_ok_shape(block, x.shape[1], x.shape[2], x.shape[3])
+def _norm_act(norm, y, cbias, relu, res=None, link=None, sums=None, s2d=False, cl=True):
+    """relu?(norm(y + cbias)), or relu(res + that), for the output y of a convolution that ran without its bias cbias (or
+    None) and a norm of a kind _norm_kind names.  cl: on the channels_last kernels (where they take y's channel count),
+    which fuse the residual and take `link` (the unit's _ResLink), `sums` (the convolution's _NormSums) and `s2d` (see _S2D);
+    else on the NCHW ones.  An InstanceNorm removes a per-channel constant again, so cbias is dropped there."""
+    kind = _norm_kind(norm)
+    if kind is None:
+        raise RuntimeError(f"no fsraft norm kernel covers {norm!r}")
+    cl = cl and _cl_channels_ok(y.shape[1])
+    assert cl or not s2d, "space-to-depth output is a feature of the fused channels_last norm kernels"
+    if kind == "instance":
+        if cl:
+            return _InstNormReluCL.apply(y, norm.eps, relu, res, link, sums, s2d)
+        y = _InstNormRelu.apply(y, norm.eps, relu)
+    else:
+        bn = (y, cbias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps, relu)
+        if cl:
+            return _FrozenBNReluCL.apply(*bn, res, link, s2d)
+        y = _FrozenBNRelu.apply(*bn)
+    return y if res is None else F.relu(res + y)
 
 
 S2D_EMIT = True   # False: the stride-2 units copy their input into the space-to-depth layout themselves
@@ -583,39 +562,30 @@ class _S2D:
 
 
 def _conv_norm(conv, norm, x, relu, to_cl=False, res=None, link=None, res_link=None, s2d=False):
-    """relu?(norm(conv(x))) of pytorch/core/extractor.py.  The convolution stays a PyTorch-ROCm (MIOpen) call; for fp32
-    CUDA tensors the normalisation + ReLU around it runs on the fused fsraft kernels:
+    """relu?(norm(conv(x))) of pytorch/core/extractor.py, or relu(res + that).  For an fp32 CUDA tensor outside autocast
+    and a norm that _norm_kind names, the convolution runs WITHOUT its bias on the route _conv picks (fsraft kernels for a
+    channels_last input or the stem, else MIOpen) and the norm + ReLU on the fsraft kernels (_norm_act):
       * non-affine InstanceNorm2d (feature encoder).  A per-channel constant added before it is removed again by its
-        mean subtraction, so the convolution runs without its bias: same output (to rounding), one bias-add kernel less
-        forward and one [N,H,W] reduction less backward.  The bias then receives no gradient (mathematically it is
-        exactly zero; parallel.FlatGradients keeps a zero for it, so the optimizer treats it as the reference does);
-      * BatchNorm2d using running statistics (context encoder after freeze_bn, or eval mode).
+        mean subtraction: same output (to rounding), one bias-add kernel less forward and one [N,H,W] reduction less
+        backward.  The bias then receives no gradient (mathematically it is exactly zero; parallel.FlatGradients keeps a
+        zero for it, so the optimizer treats it as the reference does);
+      * BatchNorm2d using running statistics (context encoder after freeze_bn, or eval mode): the bias joins the shift.
     Everything else (training-mode BatchNorm, GroupNorm, autocast dtypes, CPU) is the framework's own modules.
-    A channels_last input (or to_cl) keeps the chain channels_last: the convolution output is converted if the library
-    handed back NCHW, and the [N][HW][C] twins of the norm kernels are used."""
-    fused = x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
-    if isinstance(norm, nn.InstanceNorm2d) and not norm.affine and not norm.track_running_stats:
-        if fused:
-            sums = _NormSums() if (to_cl or _is_cl(x)) else None
-            y = _conv(conv, x, None, link, stem_cl=to_cl, sums=sums)
-            if (to_cl or _is_cl(x)) and _cl_norm_ok(y):
-                return _InstNormReluCL.apply(y, norm.eps, relu, res, res_link, sums, s2d)
-            assert not s2d
-            y = _InstNormRelu.apply(y, norm.eps, relu)
-            return y if res is None else F.relu(res + y)
-        y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups) if conv.bias is not None else conv(x)
-        y = norm(y)
-    elif isinstance(norm, nn.BatchNorm2d) and not norm.training and norm.track_running_stats and norm.affine and fused:
-        y = _conv(conv, x, None, link, stem_cl=to_cl)
-        if (to_cl or _is_cl(x)) and _cl_norm_ok(y):
-            return _FrozenBNReluCL.apply(y, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps, relu, res,
-                                         res_link, s2d)
-        assert not s2d
-        y = _FrozenBNRelu.apply(y, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps, relu)
-        return y if res is None else F.relu(res + y)
-    else:
-        y = norm(conv(x))
+    A channels_last input (or to_cl) keeps the chain channels_last: the [N][HW][C] twins of the norm kernels are used, and
+    they convert the convolution's output if the library handed back NCHW.  link / res_link: the unit's _ResLink, for its
+    first convolution / for the norm that fuses the shortcut `res`."""
+    kind = _norm_kind(norm)
+    if kind is not None and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled():
+        cl = to_cl or _is_cl(x)
+        sums = _NormSums() if (kind == "instance" and cl) else None
+        y = _conv(conv, x, None, link, stem_cl=to_cl, sums=sums)
+        return _norm_act(norm, y, conv.bias, relu, res, res_link, sums, s2d, cl)
     assert not s2d, "space-to-depth output is a feature of the fused channels_last norm kernels"
+    if kind == "instance" and conv.bias is not None:        # (as above: the bias changes nothing)
+        y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
+    else:
+        y = conv(x)
+    y = norm(y)
     y = F.relu(y, inplace=True) if relu else y
     return y if res is None else F.relu(res + y)
 
@@ -661,17 +631,10 @@ class _Block(nn.Module):
         """emit_for: the stride-2 unit that consumes this unit's output (the encoder's channels_last walk passes it): the output then
         leaves as an _S2D holder where that unit can take it."""
         if isinstance(x, _S2D):
-            y1, ys = _StridedPairFn.apply(x.t, self.conv1.weight, self.downsample[0].weight, _pair_packs(self), True)
-            y = _norm_act(self.norm1, y1, self.conv1.bias, True)
-            xs = _norm_act(self.downsample[1], ys, self.downsample[0].bias, False)
-            return _conv_norm(self.conv2, self.norm2, y, True, to_cl=True, res=xs)
+            return self._strided_pair(x.t, True)
         cl = _is_cl(x)
-        if cl and self.downsample is not None and _pair_ok(self, x):
-            # stride-2 unit, channels_last: both strided convolutions on the stride-1 kernels over the space-to-depth input
-            y1, ys = _StridedPairFn.apply(x, self.conv1.weight, self.downsample[0].weight, _pair_packs(self))
-            y = _norm_act(self.norm1, y1, self.conv1.bias, True)
-            xs = _norm_act(self.downsample[1], ys, self.downsample[0].bias, False)
-            return _conv_norm(self.conv2, self.norm2, y, True, to_cl=True, res=xs)
+        if cl and self.downsample is not None and _pair_ok(self, *x.shape[1:]):
+            return self._strided_pair(x, False)
         if cl and self.downsample is not None:
             x = _ToNCHW.apply(x)        # the strided convolutions (first 3x3 / shortcut 1x1) are MIOpen NCHW calls: one copy for both
         y = x
@@ -683,12 +646,22 @@ class _Block(nn.Module):
         for i in range(1, self.n):
             y = _conv_norm(getattr(self, f"conv{i}"), getattr(self, f"norm{i}"), y, True, to_cl=cl, link=link if i == 1 else None)
         # last convolution of the unit: relu(x + relu(norm(conv(y)))), the add and outer ReLU fused into the norm kernel
-        last = getattr(self, f"conv{self.n}")
-        emit = bool(cl and S2D_EMIT and emit_for is not None and self.downsample is None and _is_cl(y) and _cl_norm_ok(torch.empty(0, last.out_channels))
-                    and _pair_ok_shape(emit_for, last.out_channels, y.shape[2], y.shape[3])
-                    and isinstance(getattr(self, f"norm{self.n}"), (nn.InstanceNorm2d, nn.BatchNorm2d)))
-        out = _conv_norm(last, getattr(self, f"norm{self.n}"), y, True, to_cl=cl, res=x, res_link=link, s2d=emit)
+        last, norm = getattr(self, f"conv{self.n}"), getattr(self, f"norm{self.n}")
+        # (the norm's kind decides, not its class: _conv_norm asserts on s2d for a norm without a kind, a training-mode
+        #  BatchNorm say, so a unit in front of a stride-2 unit emits only what its own norm kernel can write)
+        emit = bool(cl and S2D_EMIT and emit_for is not None and self.downsample is None and _is_cl(y)
+                    and _cl_channels_ok(last.out_channels) and _pair_ok(emit_for, last.out_channels, y.shape[2], y.shape[3])
+                    and _norm_kind(norm) is not None)
+        out = _conv_norm(last, norm, y, True, to_cl=cl, res=x, res_link=link, s2d=emit)
         return _S2D(out) if emit else out
+
+    def _strided_pair(self, x, pre):
+        """Stride-2 unit, channels_last: both strided convolutions on the stride-1 kernels over the space-to-depth input.
+        pre: x already is that tensor (the `t` of an _S2D)."""
+        y1, ys = _StridedPairFn.apply(x, self.conv1.weight, self.downsample[0].weight, _pair_packs(self), pre)
+        y = _norm_act(self.norm1, y1, self.conv1.bias, True)
+        xs = _norm_act(self.downsample[1], ys, self.downsample[0].bias, False)
+        return _conv_norm(self.conv2, self.norm2, y, True, to_cl=True, res=xs)
 
 
 class ResidualBlock(_Block):
@@ -704,18 +677,10 @@ class BottleneckBlock(_Block):
 def _channels_last_ok(enc, x):
     """Channels_last encoder path: fp32 CUDA, no autocast, norms that the fused channels_last kernels cover (non-affine
     InstanceNorm, BatchNorm on running statistics).  FSRAFT_ENCODER_CL=0 keeps the encoder NCHW on MIOpen throughout."""
-    import os
     mode = int(os.environ.get("FSRAFT_ENCODER_CL", "1"))
-    if mode == 0:
+    if mode == 0 or not (x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():
         return 0
-    if not (x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():
-        return 0
-    n = enc.norm1
-    if isinstance(n, nn.InstanceNorm2d):
-        return mode if not n.affine and not n.track_running_stats else 0
-    if isinstance(n, nn.BatchNorm2d):
-        return mode if not n.training and n.track_running_stats and n.affine else 0
-    return 0
+    return mode if _norm_kind(enc.norm1) is not None else 0
 
 
 class _Encoder(nn.Module):
@@ -746,7 +711,7 @@ class _Encoder(nn.Module):
         if pair:
             n = x[0].shape[0]
             x = torch.cat(x, dim=0)
-        # channels_last after the stem (an NCHW MIOpen call: 3 input channels): the stride-1 convolutions then run on the
+        # channels_last after the stem (NCHW image in: _StemFn, or a MIOpen call): the stride-1 convolutions then run on the
         # fsraft implicit-GEMM kernels and the norm + ReLU kernels read and write [N][HW][C] directly
         cl = _channels_last_ok(self, x)
         if cl:

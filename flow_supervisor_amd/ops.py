@@ -1498,6 +1498,130 @@ def col_sum_v(v, out, scale=1.0):
     L.check(_lib().fsraft_col_sum(ctypes.c_void_p(v.ptr), v.ld, M, v.C, L.ptr(out), float(scale), L.stream()), "col_sum")
 
 
+# ------------------------------------------------------------------ encoder norm + ReLU (csrc/norm.hip, csrc/norm_cl.hip)
+# NCHW entries take contiguous tensors, the _cl_ entries channels_last ones (storage [N][H*W][C]); the callers (the autograd
+# Functions of core/extractor.py) convert.  s2w: 0, or the width W of x when the kernel's result (forward) / incoming gradient
+# (backward) is x's space-to-depth image, a [N, 4C, H/2, W/2] channels_last tensor (extractor._S2D).
+NORM_PARTIAL_ROWS = 8      # rows per image of the channels-last kernels' partial column sums (norm_cl.hip)
+
+
+def norm_partial_rows(N, C, device):
+    """Zeroed [2, N * NORM_PARTIAL_ROWS, C] accumulation target of the channels-last norm kernels and of the convolution
+    epilogue that feeds them (conv_forward's `stats`): partial column sums of two quantities per image."""
+    return zeros(2, N * NORM_PARTIAL_ROWS, C, device=device)
+
+
+def _norm_cl_out(x, s2w):
+    if not s2w:
+        return torch.empty_like(x)                            # preserves channels_last
+    N, C, H, W = x.shape
+    return torch.empty(N, H // 2, W // 2, 4 * C, device=x.device, dtype=torch.float32).permute(0, 3, 1, 2)
+
+
+def inorm_relu_fwd(x, eps, relu):
+    """relu?(instance_norm(x)), NCHW -> (y, the per-plane statistics [N * C, 2] the backward reads)."""
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)
+    stats = torch.empty(N * C, 2, device=x.device, dtype=torch.float32)
+    L.check(_lib().fsraft_inorm_relu_fwd(L.ptr(x), L.ptr(y), L.ptr(stats), N * C, H * W, float(eps), int(relu), L.stream()),
+            "inorm_relu_fwd")
+    return y, stats
+
+
+def inorm_relu_bwd(g, x, stats, relu):
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    L.check(_lib().fsraft_inorm_relu_bwd(L.ptr(g), L.ptr(x), L.ptr(stats), L.ptr(dx), N * C, H * W, int(relu), L.stream()),
+            "inorm_relu_bwd")
+    return dx
+
+
+def affine_relu_fwd(x, scale, shift, relu):
+    """relu?(x * scale[c] + shift[c]), NCHW."""
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)
+    L.check(_lib().fsraft_affine_relu_fwd(L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(y), N * C, C, H * W, int(relu), L.stream()),
+            "affine_relu_fwd")
+    return y
+
+
+def affine_relu_bwd(g, x, scale, shift, relu):
+    """-> (dx, sums [2, C]): per-channel sums of g' and of g' * x, g' = g behind the ReLU mask."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    sums = zeros(2, C, device=x.device)
+    L.check(_lib().fsraft_affine_relu_bwd(L.ptr(g), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(dx), L.ptr(sums[0]), L.ptr(sums[1]),
+                                          N * C, C, H * W, int(relu), L.stream()), "affine_relu_bwd")
+    return dx, sums
+
+
+def inorm_relu_cl_fwd(x, res, eps, relu, acc=None, s2w=0):
+    """relu?(instance_norm(x)), or relu(res + that) with the shortcut `res` -> (y, statistics [N, C, 2]).  acc: partial rows
+    already filled by the convolution that produced x (norm_partial_rows; any other shape is ignored), which spare the
+    kernel its own statistics pass."""
+    N, C, H, W = x.shape
+    y = _norm_cl_out(x, s2w)
+    have = acc is not None and tuple(acc.shape) == (2, N * NORM_PARTIAL_ROWS, C)
+    if not have:
+        acc = norm_partial_rows(N, C, x.device)
+    stats = torch.empty(N, C, 2, device=x.device, dtype=torch.float32)
+    L.check(_lib().fsraft_inorm_relu_cl_fwd(L.ptr(x), L.ptr(res), L.ptr(y), L.ptr(acc[0]), L.ptr(acc[1]), L.ptr(stats), N, H * W, C,
+                                            float(eps), int(relu), int(have), s2w, L.stream()), "inorm_relu_cl_fwd")
+    return y, stats
+
+
+def inorm_relu_cl_bwd(g, x, stats, out, relu, s2w=0):
+    """out: the forward's result when it had a shortcut, else None -> (dx, dres or None)."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if out is not None else None
+    acc = norm_partial_rows(N, C, x.device)
+    L.check(_lib().fsraft_inorm_relu_cl_bwd(L.ptr(g), L.ptr(x), L.ptr(stats), L.ptr(out), L.ptr(acc[0]), L.ptr(acc[1]), L.ptr(dx),
+                                            L.ptr(dres), N, H * W, C, int(relu), s2w, L.stream()), "inorm_relu_cl_bwd")
+    return dx, dres
+
+
+def bn_fold(weight, bias, rm, rv, cbias, eps):
+    """A BatchNorm on running statistics behind a convolution that ran without its bias `cbias` (or None), as
+    y = x * scale + shift -> (scale, shift, rs = rsqrt(rv + eps), rmc = rm - cbias): the rows of one [4, C] buffer, one launch."""
+    C = weight.shape[0]
+    fold = torch.empty(4, C, device=weight.device, dtype=torch.float32)
+    L.check(_lib().fsraft_bn_fold(L.ptr(weight.detach().float().contiguous()), L.ptr(bias.detach().float().contiguous()),
+                                  L.ptr(rm.float().contiguous()), L.ptr(rv.float().contiguous()),
+                                  L.ptr(cbias.detach().float().contiguous()) if cbias is not None else None, float(eps), C,
+                                  L.ptr(fold[0]), L.ptr(fold[1]), L.ptr(fold[2]), L.ptr(fold[3]), L.stream()), "bn_fold")
+    return fold.unbind(0)
+
+
+def bn_fold_bwd(part, rs, rmc, scale, want_dcbias):
+    """Partial rows of affine_relu_cl_bwd -> (dweight, dbias, dcbias or None), one launch."""
+    C = part.shape[2]
+    dpar = torch.empty(3, C, device=part.device, dtype=torch.float32)
+    L.check(_lib().fsraft_bn_fold_bwd(L.ptr(part), part.shape[1], C, L.ptr(rs), L.ptr(rmc), L.ptr(scale), L.ptr(dpar[0]), L.ptr(dpar[1]),
+                                      L.ptr(dpar[2]) if want_dcbias else None, L.stream()), "bn_fold_bwd")
+    return dpar[0], dpar[1], (dpar[2] if want_dcbias else None)
+
+
+def affine_relu_cl_fwd(x, res, scale, shift, relu, s2w=0):
+    """relu?(x * scale[c] + shift[c]), or relu(res + that) with the shortcut `res`."""
+    N, C, H, W = x.shape
+    y = _norm_cl_out(x, s2w)
+    L.check(_lib().fsraft_affine_relu_cl_fwd(L.ptr(x), L.ptr(res), L.ptr(scale), L.ptr(shift), L.ptr(y), N * H * W, C, int(relu), H * W,
+                                             s2w, L.stream()), "affine_relu_cl_fwd")
+    return y
+
+
+def affine_relu_cl_bwd(g, x, scale, shift, out, relu, s2w=0):
+    """out as in inorm_relu_cl_bwd -> (dx, dres or None, the partial rows bn_fold_bwd reduces)."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if out is not None else None
+    part = norm_partial_rows(N, C, x.device)
+    L.check(_lib().fsraft_affine_relu_cl_bwd(L.ptr(g), L.ptr(x), L.ptr(scale), L.ptr(shift), L.ptr(out), L.ptr(dx), L.ptr(dres),
+                                             L.ptr(part[0]), L.ptr(part[1]), N, H * W, C, int(relu), s2w, L.stream()), "affine_relu_cl_bwd")
+    return dx, dres, part
+
+
 # ------------------------------------------------------------------ validation metrics
 def flow_metrics_scratch_bytes(B, H, W):
     n = _lib().fsraft_flow_metrics_scratch_bytes(B, H, W)

@@ -1492,6 +1492,50 @@ def test_encoder_strided_pair_space_to_depth(B, C, N, H, W, precision):
     close(got[2], blk.downsample[0].weight.grad, 1e-4 * f, 1e-4, what="shortcut dw")
 
 
+def _same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32).flatten(), b.contiguous().view(torch.int32).flatten())
+
+
+def test_encoder_weight_pack_records_hold_what_their_fields_name(precision):
+    """extractor._ConvPacks / _PairPacks (the cached weight images _ConvCL and _StridedPairFn read by field name): every field
+    bit-equal to ops.pack_weight in the mode its name promises (fragment packs: ops.fragment_order of it); an fp32 field
+    that no kernel reads -- split arithmetic and more than 32 rows on that side -- IS the split field; fragment packs only
+    for 3x3 with 33..64 channels on the GEMM's k side.  Pair packs against the host statement of the rewrite (_s2d_weight)."""
+    from flow_supervisor_amd import ops
+    from flow_supervisor_amd.core.extractor import ResidualBlock, _pair_packs, _s2d_weight, _weight_packs
+    torch.manual_seed(17)
+    split = precision == "split"
+
+    def check(p, w, src_c, what):
+        cout, cin = w.shape[0], src_c[0]
+        for field, mode, rows in (("fwd", 0, cout), ("dgrad", 1, cin)):
+            fp32, sp = getattr(p, field), getattr(p, field + "_split")
+            assert _same_bits(sp, ops.pack_weight(w, src_c, 10 + mode)), (what, field + "_split")
+            if split and rows > 32:
+                assert fp32 is sp, (what, field, "the split pack stands in for the fp32 one")
+            else:
+                assert fp32 is not sp and _same_bits(fp32, ops.pack_weight(w, src_c, mode)), (what, field)
+
+    for conv, frags in ((torch.nn.Conv2d(48, 40, 3, padding=1), True), (torch.nn.Conv2d(24, 24, 1), False),
+                        (torch.nn.Conv2d(128, 128, 3, padding=1), False)):
+        conv = conv.to(DEV)
+        p, w = _weight_packs(conv), conv.weight.detach()
+        what = f"{conv.in_channels}->{conv.out_channels} k{conv.kernel_size[0]}"
+        assert p._fields == ("key", "fwd", "fwd_split", "dgrad", "dgrad_split", "fwd_frag", "dgrad_frag") and p is conv.__dict__["_fs_packs"]
+        check(p, w, [conv.in_channels], what)
+        if frags:
+            assert _same_bits(p.fwd_frag, ops.fragment_order(ops.pack_weight(w, [conv.in_channels], 10))), what
+            assert _same_bits(p.dgrad_frag, ops.fragment_order(ops.pack_weight(w, [conv.in_channels], 11))), what
+        else:
+            assert p.fwd_frag is None and p.dgrad_frag is None, what
+    # (24 -> 24: both sides at most 32 rows, so the fp32 packs are built in either mode; 128 -> 128: reused in split mode)
+    blk = ResidualBlock(8, 16, "instance", stride=2).to(DEV)
+    pp = _pair_packs(blk)
+    assert pp._fields == ("key", "conv3", "shortcut") and pp is blk.__dict__["_fs_pair_packs"]
+    check(pp.conv3, _s2d_weight(blk.conv1.weight.detach()).contiguous(), [32], "pair 3x3 as 2x2 over space-to-depth")
+    check(pp.shortcut, blk.downsample[0].weight.detach(), [8], "pair shortcut")
+
+
 @pytest.mark.parametrize("C,N,B,H,W,carried", [(64, 64, 2, 184, 250, True), (96, 96, 2, 184, 250, True), (128, 128, 8, 55, 128, True),
                                                (128, 128, 3, 55, 128, False), (64, 64, 1, 20, 24, False)])
 def test_instance_norm_statistics_from_the_convolution_epilogue(C, N, B, H, W, carried):

@@ -223,3 +223,35 @@ def test_bench_restores_the_initial_state_in_place():
     assert [t.data_ptr() for t in now] == held
     assert all(torch.equal(t, v) for t, v in zip(now, initial))
     assert all(float(v.abs().sum()) == 0 for v in state)
+
+
+def test_norm_kind_names_the_norms_the_fused_kernels_cover():
+    """extractor._norm_kind, the one classification every encoder route goes by: "instance" needs no affine parameters and no
+    running statistics, "frozen_bn" an affine BatchNorm2d that is not training and tracks running statistics."""
+    import torch.nn as nn
+    from flow_supervisor_amd.core.extractor import _norm_kind
+    assert _norm_kind(nn.InstanceNorm2d(8)) == "instance"
+    assert _norm_kind(nn.InstanceNorm2d(8, affine=True)) is None
+    assert _norm_kind(nn.InstanceNorm2d(8, track_running_stats=True)) is None
+    assert _norm_kind(nn.BatchNorm2d(8).train()) is None
+    assert _norm_kind(nn.BatchNorm2d(8).eval()) == "frozen_bn"
+    assert _norm_kind(nn.BatchNorm2d(8, affine=False).eval()) is None
+    assert _norm_kind(nn.BatchNorm2d(8, track_running_stats=False).eval()) is None
+    assert _norm_kind(nn.GroupNorm(2, 8)) is None
+    assert _norm_kind(nn.Sequential()) is None
+
+
+def test_stride_two_pair_predicates(monkeypatch):
+    """Which units take the space-to-depth pair: by module structure (what the weight packer goes by), and for a given input
+    size (what the forward pass goes by)."""
+    from flow_supervisor_amd.core import extractor as E
+    unit = E.ResidualBlock(64, 96, "instance", 2)
+    assert E._pair_structure_ok(unit) is True
+    assert E._pair_structure_ok(E.ResidualBlock(64, 64, "instance", 1)) is False
+    assert E._pair_structure_ok(E.BottleneckBlock(32, 64, "instance", 2)) is False          # n == 3: the stride sits on conv2
+    assert E._pair_ok(unit, 64, 46, 62)
+    assert not E._pair_ok(unit, 64, 45, 62) and not E._pair_ok(unit, 64, 46, 61)           # odd H / odd W
+    assert not E._pair_ok(unit, 62, 46, 62)                                                 # channels: no multiple of four
+    assert not E._pair_ok(E.ResidualBlock(64, 64, "instance", 1), 64, 46, 62)
+    monkeypatch.setattr(E, "S2D_UNITS", False)
+    assert not E._pair_ok(unit, 64, 46, 62)

@@ -25,8 +25,6 @@ reference's extension returns an all-zero coords_grad there (correlation_kernel.
 ``AlternateCorrBlock(..., coords_grad=True)`` gives the same gradient as ``CorrBlock`` from
 fsraft_altcorr_fused_dcoords (csrc/altcorr_dcoords.hip), still without the volume.
 """
-import math
-
 import torch
 import torch.nn.functional as F
 
@@ -101,21 +99,32 @@ class _BuildFn(torch.autograd.Function):
         return d1, d2, None, None, None
 
 
+def _in_convention(coords, is_flow, want_flow):
+    """A lookup's coordinates (is_flow: its flow) in the other convention when `want_flow` differs: a block looked up both ways
+    keeps one convention in its stash."""
+    if is_flow == want_flow:
+        return coords
+    B, _, H, W = coords.shape
+    g = coords_grid(B, H, W, device=coords.device)
+    return coords - g if want_flow else coords + g
+
+
 class _LookupFn(torch.autograd.Function):
-    """One lookup.  anchor: the build node's 1-element output (None for a block whose feature maps take no gradient: the node
-    then exists for the coordinate gradient alone).  The volume gradient is not formed here -- backward hands (coords, dOut) to
-    the block's state -- but the coordinate gradient is: when `coords` requires grad, backward returns
-    ops.corr_lookup_tiled_dcoords(...), a gather over the same windows the forward read.  Only in that case the node keeps the
-    volume tensor and its layout (not the block: see the reference-cycle note in _AltBuildFn), so the volume then lives until
-    this node's backward has run or the graph is freed; with detached coordinates nothing but the coordinates is kept."""
+    """One lookup of either block.  anchor: the build node's 1-element output (None for a block whose feature maps take no
+    gradient: the node then exists for the coordinate gradient alone).  The volume gradient is not formed here -- backward hands
+    (coords, dOut) to the block's state -- but the coordinate gradient is: when `coords` requires grad, backward returns the
+    block's `_dcoords()` op on them, a gather over the same windows the forward read.  Only in that case the node keeps the
+    tensors that op reads (CorrBlock: the volume, which then lives until this node's backward has run or the graph is freed;
+    AlternateCorrBlock: the channels-last maps) -- never the block: see the reference-cycle note in _AltBuildFn; with detached
+    coordinates nothing but the coordinates is kept."""
 
     @staticmethod
     def forward(ctx, anchor, coords, block, channels_last, is_flow, out_buf=None):
-        out = ops.corr_lookup_tiled_fwd(block._vol, block._lay, coords, block.radius, is_flow, out=out_buf)
+        out = block._lookup(coords, is_flow, out_buf)
         ctx.state = block._state if anchor is not None else None
         ctx.cl, ctx.is_flow = channels_last, is_flow
         if ctx.needs_input_grad[1]:
-            ctx.vol, ctx.lay, ctx.radius = block._vol, block._lay, block.radius
+            ctx.dcoords, ctx.radius = block._dcoords(), block.radius
         ctx.save_for_backward(coords)
         return out if channels_last else ops.nhwc_to_nchw(out)
 
@@ -125,24 +134,51 @@ class _LookupFn(torch.autograd.Function):
         dout = dout.contiguous() if ctx.cl else ops.nchw_to_nhwc(dout)
         dcoords = None
         if ctx.needs_input_grad[1]:
-            dcoords = ops.corr_lookup_tiled_dcoords(ctx.vol, ctx.lay, coords, dout, ctx.radius, ctx.is_flow)
-            ctx.vol = None
+            op, a, b = ctx.dcoords
+            dcoords = op(a, b, coords, dout, ctx.radius, ctx.is_flow)
+            ctx.dcoords = None
         if ctx.state is not None:
-            if ctx.is_flow != ctx.state.is_flow:       # (a block looked up both ways: keep one convention in the stash)
-                B, _, H, W = coords.shape
-                g = coords_grid(B, H, W, device=coords.device)
-                coords = coords - g if ctx.state.is_flow else coords + g
-            ctx.state.stash.append((coords, dout))
+            ctx.state.stash.append((_in_convention(coords, ctx.is_flow, ctx.state.is_flow), dout))
         return None, dcoords, None, None, None, None   # (no gradient tensor for the anchor: the build node still runs after every lookup)
 
 
-class CorrBlock:
+class _Lookups:
+    """`block(coords)` of both blocks.  A block has _tracks_grad, _anchor, _state, coords_grad (whether a lookup honours
+    coordinates that require grad), _lookup(coords, is_flow, out) -- the forward op -- and _dcoords() -- the coordinate-gradient
+    op and the two tensors it reads, called as op(a, b, coords, dout, radius, is_flow)."""
+
+    @on_tensor_device
+    def __call__(self, coords, channels_last=False, is_flow=False, out=None):
+        """coords [B,2,H,W] (x,y).  Returns [B, L*(2r+1)^2, H, W] contiguous (or [B,H,W,C] when
+        channels_last=True, the layout our update block consumes directly).  is_flow=True: the tensor holds the flow and
+        the lookup is centred on pixel grid + flow (what the RAFT loop passes: it never forms coords1).  out (channels_last
+        only): a preallocated [B,H,W,C] buffer the lookup writes into (update.MotionBatch's slots).
+        Differentiable in `coords` (in the flow when is_flow: the same gradient) when they require grad and the block has
+        coords_grad; detached coordinates run the nodes and launches they always did."""
+        coords = coords.float()
+        if out is not None and not channels_last:
+            raise ValueError("out= is for channels_last lookups")
+        grad_on = torch.is_grad_enabled()
+        coords_grad = self.coords_grad and grad_on and coords.requires_grad
+        if self._tracks_grad and grad_on:
+            if not self._state.stash:
+                self._state.is_flow = is_flow
+            return _LookupFn.apply(self._anchor, coords if coords_grad else coords.detach(), self, channels_last, is_flow, out)
+        if coords_grad:       # feature maps without gradient: the same node without an anchor, for the coordinate gradient alone
+            return _LookupFn.apply(None, coords, self, channels_last, is_flow, out)
+        res = self._lookup(coords, is_flow, out)
+        return res if channels_last else ops.nhwc_to_nchw(res)
+
+
+class CorrBlock(_Lookups):
     """All-pairs volume + pyramid + lookup (pytorch/core/corr.py:13-60).  The volume lives in the tiled-row layout of
     csrc/corr_layout.hpp (one row per query, all levels, 4x4-cell tiles); `corr_pyramid` -- the reference's list of
     [B*H*W, 1, h_l, w_l] tensors -- is materialised from it on first access (API edge; nothing on the path reads it).
     grad_samples (extension, default None): the caller vouches that only the lookups of the first k samples receive gradient
     (core/l2l.py: the supervisor phase of a batched flow-supervisor step); the backward then builds and contracts the gradient
     volume of those samples only."""
+
+    coords_grad = True
 
     @on_tensor_device
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4, grad_samples=None):
@@ -172,27 +208,11 @@ class CorrBlock:
             self._pyr = [self._lay.level_view(self._vol, l) for l in range(self.num_levels)]
         return self._pyr
 
-    @on_tensor_device
-    def __call__(self, coords, channels_last=False, is_flow=False, out=None):
-        """coords [B,2,H,W] (x,y).  Returns [B, L*(2r+1)^2, H, W] contiguous (or [B,H,W,C] when
-        channels_last=True, the layout our update block consumes directly).  is_flow=True: the tensor holds the flow and
-        the lookup is centred on pixel grid + flow (what the RAFT loop passes: it never forms coords1).  out (channels_last
-        only): a preallocated [B,H,W,C] buffer the lookup writes into (update.MotionBatch's slots).
-        Differentiable in `coords` (in the flow when is_flow: the same gradient) when they require grad; detached coordinates
-        run the nodes and launches they always did."""
-        coords = coords.float()
-        if out is not None and not channels_last:
-            raise ValueError("out= is for channels_last lookups")
-        grad_on = torch.is_grad_enabled()
-        coords_grad = grad_on and coords.requires_grad
-        if self._tracks_grad and grad_on:
-            if not self._state.stash:
-                self._state.is_flow = is_flow
-            return _LookupFn.apply(self._anchor, coords if coords_grad else coords.detach(), self, channels_last, is_flow, out)
-        if coords_grad:       # feature maps without gradient: the same node without an anchor, for the coordinate gradient alone
-            return _LookupFn.apply(None, coords, self, channels_last, is_flow, out)
-        res = ops.corr_lookup_tiled_fwd(self._vol, self._lay, coords, self.radius, is_flow, out=out)
-        return res if channels_last else ops.nhwc_to_nchw(res)
+    def _lookup(self, coords, is_flow, out):
+        return ops.corr_lookup_tiled_fwd(self._vol, self._lay, coords, self.radius, is_flow, out=out)
+
+    def _dcoords(self):
+        return ops.corr_lookup_tiled_dcoords, self._vol, self._lay
 
     @staticmethod
     @on_tensor_device
@@ -232,42 +252,7 @@ class _AltBuildFn(torch.autograd.Function):
         return d1, d2, None, None, None, None
 
 
-class _AltLookupFn(torch.autograd.Function):
-    """One lookup of AlternateCorrBlock.  anchor: the build node's 1-element output (None for a block whose feature maps take no
-    gradient: the node then exists for the coordinate gradient alone, AlternateCorrBlock(coords_grad=True)).  Backward hands
-    (coords, dOut) to the block's state for the chunked feature backward; when `coords` requires grad it also returns
-    ops.altcorr_fused_dcoords(...), computed from the channels-last maps the forward read.  Only in that case the node keeps
-    those tensors (not the block: see the reference-cycle note in _AltBuildFn)."""
-
-    @staticmethod
-    def forward(ctx, anchor, coords, block, channels_last, is_flow, out_buf=None):
-        out = ops.altcorr_fused_fwd(block._f1, block._f2, coords, block.radius, is_flow, recs=block._recs, out=out_buf)
-        ctx.state = block._state if anchor is not None else None
-        ctx.cl, ctx.is_flow = channels_last, is_flow
-        if ctx.needs_input_grad[1]:
-            ctx.f1, ctx.f2, ctx.radius = block._f1, list(block._f2), block.radius
-        ctx.save_for_backward(coords)
-        return out if channels_last else ops.nhwc_to_nchw(out)
-
-    @staticmethod
-    def backward(ctx, dout):
-        coords = ctx.saved_tensors[0].detach()
-        st = ctx.state
-        dout = dout.contiguous() if ctx.cl else ops.nchw_to_nhwc(dout)
-        dcoords = None
-        if ctx.needs_input_grad[1]:
-            dcoords = ops.altcorr_fused_dcoords(ctx.f1, ctx.f2, coords, dout, ctx.radius, ctx.is_flow)
-            ctx.f1 = ctx.f2 = None
-        if st is not None:
-            if ctx.is_flow != st.is_flow:
-                B, _, H, W = coords.shape
-                g = coords_grid(B, H, W, device=coords.device)
-                coords = coords - g if st.is_flow else coords + g
-            st.stash.append((coords, dout))
-        return None, dcoords, None, None, None, None
-
-
-class AlternateCorrBlock:
+class AlternateCorrBlock(_Lookups):
     """Memory-efficient correlation (pytorch/core/corr.py:63-91 + alt_cuda_corr): the same numbers as CorrBlock without the
     N x N volume.  One fused launch per lookup (all levels, channels-last, scaled); the backward the reference compiled but
     never wired is live here: lookups only stash (coords, dOut), the feature gradients are formed once per step from
@@ -317,18 +302,8 @@ class AlternateCorrBlock:
                 B = fmap1.shape[0]
                 self._recs = (ops.to_records(self._f1.view(B, -1, C)), [ops.to_records(f.view(B, -1, C)) for f in self._f2])
 
-    @on_tensor_device
-    def __call__(self, coords, channels_last=False, is_flow=False, out=None):
-        coords = coords.float()
-        if out is not None and not channels_last:
-            raise ValueError("out= is for channels_last lookups")
-        grad_on = torch.is_grad_enabled()
-        coords_grad = self.coords_grad and grad_on and coords.requires_grad
-        if self._tracks_grad and grad_on:
-            if not self._state.stash:
-                self._state.is_flow = is_flow
-            return _AltLookupFn.apply(self._anchor, coords if coords_grad else coords.detach(), self, channels_last, is_flow, out)
-        if coords_grad:       # feature maps without gradient: the same node without an anchor, for the coordinate gradient alone
-            return _AltLookupFn.apply(None, coords, self, channels_last, is_flow, out)
-        res = ops.altcorr_fused_fwd(self._f1, self._f2, coords, self.radius, is_flow, recs=self._recs, out=out)
-        return res if channels_last else ops.nhwc_to_nchw(res)
+    def _lookup(self, coords, is_flow, out):
+        return ops.altcorr_fused_fwd(self._f1, self._f2, coords, self.radius, is_flow, recs=self._recs, out=out)
+
+    def _dcoords(self):
+        return ops.altcorr_fused_dcoords, self._f1, list(self._f2)

@@ -8,14 +8,12 @@ padding happens directly on the channels-last hidden state.
 """
 import torch
 import torch.nn.functional as F
-from torch.amp import autocast
 
 from . import streams
-from .corr import AlternateCorrBlock, CorrBlock
-from .extractor import _prepare_packs
-from .raft import RAFT, convex_upsample
+from .corr import CorrBlock
+from .gma import mark_records
+from .raft import RAFT, normalise, refine
 from .update import BasicUpdateBlock, to_channels_last
-from .utils.utils import upflow8
 from .._lib import on_tensor_device
 
 
@@ -79,152 +77,100 @@ def _crop_back(flow_up, ox_l, oy_l, orig):
     return _CropBackFn.apply(flow_up, ox_l, oy_l, orig)
 
 
-class L2L(RAFT):
+class _FlowSupervisor:
+    """The two-phase forward of L2L and GMAL2L (mixed in before RAFT / RAFTGMA).  A class supplies `_supervisor` and
+    `_uncropped_context`."""
+
+    def _uncropped(self, ci1, ci2, sup_grad_samples):
+        """Second feature pair, context (and attention) of the uncropped frames (l2l.py:95-101): (tfmap1, tfmap2, inp, attention, k)."""
+        k = sup_grad_samples
+        k = k if (k is not None and 0 < k < ci1.shape[0] and torch.is_grad_enabled()) else None
+        if k is not None:
+            # (extension) the caller's loss reaches the supervisor's predictions of the first k samples only (the flow-supervisor
+            # step batches its labelled and its unlabelled sample: train.SemiTrainStep): the uncropped frames of the others are
+            # encoded without a graph -- their gradient would be zeros pushed through the whole feature encoder
+            ta1, ta2 = self._features(ci1[:k], ci2[:k])
+            with torch.no_grad():
+                tb1, tb2 = self._features(ci1[k:], ci2[k:])
+            t1, t2 = torch.cat([ta1, tb1]), torch.cat([ta2, tb2])
+        else:
+            t1, t2 = self._features(ci1, ci2)
+        with torch.no_grad():             # (detached by the reference, l2l.py:104: no graph, no saved activations)
+            inp, attention = self._uncropped_context(ci1)
+        return t1, t2, inp, attention, k
+
+    def _switch(self, net, flow, crop, frame, uncropped, early):
+        """Half-way (l2l.py:79-113): the student's state zero-padded into the uncropped frame's grid, the second volume and its
+        first lookup, everything detached -> (corr_fn, net, inp, attention, flow, corr).  The crop's own volume is not looked up
+        here (the reference does, l2l.py:73, and drops the result, :102).  early: the uncropped frames' encodings when the second
+        stream already has them."""
+        net, flow = _pad_state(net, flow.detach(), crop[0], crop[1], crop[2], frame)               # (l2l.py:90-93)
+        if early is not None:
+            streams.join(net.device, *early[:4])
+        tfmap1, tfmap2, inp, attention, k = early if early is not None else uncropped()
+        corr_fn = CorrBlock(tfmap1, tfmap2, radius=self.args.corr_radius, grad_samples=k)          # second volume (l2l.py:101)
+        corr = corr_fn(flow, channels_last=True, is_flow=True)          # (outside any batch: its features are detached next)
+        net, corr, inp, flow = net.detach(), corr.detach(), inp.detach(), flow.detach()
+        if attention is not None:         # (GMAL2L: the uncropped frames' attention map, still marked as records)
+            attention = mark_records(attention.detach(), like=attention)
+        return corr_fn, net, inp, attention, flow, corr
+
+    def _two_phase(self, image1, image2, ci1, ci2, ox, oy, iters, flow_init, test_mode, supervisor_grad, sup_grad_samples):
+        image1, image2 = normalise(image1), normalise(image2)
+        if ci1 is not None:
+            ci1, ci2 = normalise(ci1), normalise(ci2)
+        if test_mode:                     # the student alone (l2l.py:130-131); its context after the features, on the caller's stream
+            return self._single_phase(image1, image2, iters, flow_init, True, overlap=False)
+        if ci1 is None:
+            # the reference reads oy_/ox_ in the second half without having set them (l2l.py:124-125)
+            raise NameError(f"{type(self).__name__}.forward in training mode needs the uncropped pair ci1/ci2 and offsets ox/oy")
+        if iters == 0:                    # (no iteration, no switch: nothing is predicted)
+            return []
+        grad_mode = torch.is_grad_enabled()
+        uncropped = lambda: self._uncropped(ci1, ci2, sup_grad_samples)
+
+        def early():
+            # the uncropped frames' encodings depend on the inputs only: issued on the second stream behind the student's context,
+            # joined at the switch where the reference computes them (core/streams.py; 56.0 -> 58.8 pairs/s at one pair per GPU)
+            with torch.set_grad_enabled(grad_mode and supervisor_grad):
+                return uncropped()
+        corr_fn, (net, inp, attention), flow, side = self._encode(image1, image2, flow_init, side_work=early)
+        half = iters // 2
+        crop = (_offsets(ox, net.shape[0]), _offsets(oy, net.shape[0]), tuple(image1.shape[-2:]))
+        net, flow, _, student = refine(self.update_block, corr_fn, net, inp, flow, half, attention, motion_iters=half)
+        try:
+            if not supervisor_grad:
+                # (extension, default off) the caller's loss does not reach the supervisor's predictions -- sequence_loss_unsup
+                # only reads the last one, detached (train.py:110-111) -- so the second half records no graph, and has no
+                # HeadBatch: its predictions are upsampled per iteration
+                torch.set_grad_enabled(False)
+            corr_fn, net, inp, attention, flow, corr = self._switch(net, flow, crop, tuple(ci1.shape[-2:]), uncropped, side)
+            block, motion_iters = self._supervisor(iters - half)
+            supervisor = refine(block, corr_fn, net, inp, flow, iters - half, attention, grad_samples=sup_grad_samples,
+                                first_corr=corr, motion_iters=motion_iters)[3]
+        finally:
+            torch.set_grad_enabled(grad_mode)
+        # the deferred mask head + upsampler of each phase, after the caller's gradient mode is back (the unlabelled pass of the
+        # flow-supervisor step switches it off for the supervisor's half); the student's first.  The supervisor's full-frame
+        # predictions are cut back to the student's window here (l2l.py:124-125).
+        return student() + [_crop_back(p, *crop) for p in supervisor()]
+
+
+class L2L(_FlowSupervisor, RAFT):
     def __init__(self, args):
         super().__init__(args)
         self.grad_update_block = BasicUpdateBlock(self.args, hidden_dim=self.hidden_dim)   # l2l.py:27
 
+    def _supervisor(self, n):
+        """-> the block of the supervisor phase's n iterations and how many of them go through a MotionBatch: all but the first,
+        whose correlation features are detached."""
+        return self.grad_update_block, n - 1
+
+    def _uncropped_context(self, img):
+        """-> (inp, attention) of an uncropped frame; the hidden-state half of the context encoder's output is not used."""
+        return to_channels_last(torch.relu(self._context_split(img)[1])), None
+
     @on_tensor_device
     def forward(self, image1, image2, ci1=None, ci2=None, ox=None, oy=None, iters=24, flow_init=None,
                 upsample=True, test_mode=False, supervisor_grad=True, sup_grad_samples=None):
-        norm = lambda im: (2 * (im / 255.0) - 1.0).contiguous()
-        image1, image2 = norm(image1), norm(image2)
-        if ci1 is not None:
-            ci1, ci2 = norm(ci1), norm(ci2)
-        hdim, cdim = self.hidden_dim, self.context_dim
-        amp = False          # args.mixed_precision: no autocast here, see utils.warn_mixed_precision (fp32 storage everywhere, at full speed)
-        if not test_mode and ci1 is None:
-            # the reference reads oy_/ox_ in the second half without having set them (l2l.py:124-125)
-            raise NameError("L2L.forward in training mode needs the uncropped pair ci1/ci2 and offsets ox/oy")
-
-        def features(a, b):
-            with autocast("cuda", enabled=amp):
-                f1, f2 = self.fnet([a, b])
-            return f1.float(), f2.float()
-
-        def context(a):
-            with autocast("cuda", enabled=amp):
-                c = self.cnet(a)
-            return torch.split(c.float(), [hdim, cdim], dim=1)
-
-        def uncropped(B_):
-            """Second feature pair + context of the uncropped frames (l2l.py:95-101): (tfmap1, tfmap2, inp, k)."""
-            k = sup_grad_samples
-            if k is not None and 0 < k < B_ and torch.is_grad_enabled():
-                # (extension) the caller's loss reaches the supervisor's predictions of the first k samples only
-                # (the flow-supervisor step batches its labelled and its unlabelled sample: train.SemiTrainStep): the
-                # uncropped frames of the others are encoded without a graph -- their gradient would be zeros
-                # pushed through the whole feature encoder
-                ta1, ta2 = features(ci1[:k], ci2[:k])
-                with torch.no_grad():
-                    tb1, tb2 = features(ci1[k:], ci2[k:])
-                t1, t2 = torch.cat([ta1, tb1]), torch.cat([ta2, tb2])
-            else:
-                t1, t2 = features(ci1, ci2)
-            with torch.no_grad():         # (detached by the reference, l2l.py:104: no graph, no saved activations)
-                _, inp2 = context(ci1)
-                inp2 = to_channels_last(torch.relu(inp2))
-            return t1, t2, inp2, (k if (k is not None and 0 < k < B_) else None)
-
-        early = None
-        if streams.OVERLAP and not test_mode and ci1 is not None and image1.is_cuda and iters // 2 < iters:
-            # the uncropped frames' encodings depend on the inputs only: issued now on the second stream, joined at the switch
-            # iteration where the reference computes them (core/streams.py; 56.0 -> 58.8 pairs/s at one pair per GPU)
-            _prepare_packs(self.fnet)                   # (the packed weights both streams read are built on this one first)
-            _prepare_packs(self.cnet)
-            with torch.cuda.stream(streams.fork(image1.device)):
-                # the student's own context first (the loop waits for it, and only for it: the event), then the uncropped frames
-                net, inp = context(image1)
-                net, inp = to_channels_last(torch.tanh(net)), to_channels_last(torch.relu(inp))
-                ctx_done = streams.mark(image1.device)
-                with torch.set_grad_enabled(torch.is_grad_enabled() and supervisor_grad):
-                    early = uncropped(image1.shape[0])
-        fmap1, fmap2 = features(image1, image2)
-        if self.args.alternate_corr:
-            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, coords_grad=getattr(self.args, "alt_coords_grad", False))
-        else:
-            corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
-        if early is not None:
-            streams.join(image1.device, net, inp, event=ctx_done)
-        else:
-            net, inp = context(image1)
-            net = to_channels_last(torch.tanh(net))
-            inp = to_channels_last(torch.relu(inp))
-
-        # As in RAFT.forward the loop carries the FLOW, not coords1 = coords0 + flow (l2l.py:66-70, 110-122): the lookups add
-        # the pixel grid themselves, so an iteration has one framework op (flow + delta) instead of three; same gradient
-        # structure -- the flow entering an iteration is detached.
-        B, _, Hi, Wi = image1.shape
-        flow = flow_init.float() if flow_init is not None else torch.zeros(B, 2, Hi // 8, Wi // 8, device=image1.device)
-
-        flow_predictions = []
-        flow_up = None
-        half = iters // 2
-        crop = None
-        grad_mode = torch.is_grad_enabled()
-        # training: mask head + upsampler of a phase's iterations as one launch each after the loop (update.HeadBatch), one batch
-        # per phase (the two phases run different blocks on different grids)
-        hb = self.update_block.head_batch(half, net) if not test_mode else None
-        mb = self.update_block.motion_batch(half, net) if not test_mode else None      # (update.MotionBatch; the student's phase)
-        hb2, mb2, flows, flows2 = None, None, [], []
-        try:
-            for itr in range(iters):
-                if itr == half and not supervisor_grad and not test_mode:
-                    # (extension, default off) the caller's loss does not reach the supervisor's predictions -- sequence_loss_unsup
-                    # only reads the last one, detached (train.py:110-111) -- so the second half records no graph
-                    torch.set_grad_enabled(False)
-                flow = flow.detach()
-                if test_mode or itr != half:          # (at the switch the reference looks up the crop's volume and drops it, l2l.py:73/102)
-                    cur_mb = None if test_mode else (mb if itr < half else mb2)
-                    slot = {"out": cur_mb.corr[cur_mb.n]} if cur_mb is not None else {}
-                    corr = corr_fn(flow, channels_last=True, is_flow=True, **slot)
-                want_up = not test_mode or itr == iters - 1          # test_mode keeps only the last flow_up (l2l.py:130-131)
-                if test_mode or itr < half:
-                    net, up_mask, delta_flow = self.update_block.forward_cl(net, inp, corr, flow, need_mask=want_up, head_batch=hb,
-                                                                            motion_batch=None if test_mode else mb)
-                else:
-                    if itr == half:
-                        if ci1 is not None:
-                            crop = (_offsets(ox, net.shape[0]), _offsets(oy, net.shape[0]), tuple(image1.shape[-2:]))
-                            net, flow = _pad_state(net, flow, crop[0], crop[1], crop[2], tuple(ci1.shape[-2:]))   # (l2l.py:90-93)
-                            if early is not None:
-                                streams.join(net.device, *early[:3])
-                                tfmap1, tfmap2, inp, k = early
-                                early = None
-                            else:
-                                tfmap1, tfmap2, inp, k = uncropped(net.shape[0])
-                            corr_fn = CorrBlock(tfmap1, tfmap2, radius=self.args.corr_radius, grad_samples=k)   # second volume (l2l.py:101)
-                            corr = corr_fn(flow, channels_last=True, is_flow=True)
-                        net, corr, inp, flow = net.detach(), corr.detach(), inp.detach(), flow.detach()
-                        hb2 = self.grad_update_block.head_batch(iters - half, net)
-                        # (the switch iteration's own correlation features are detached: it runs outside the batch)
-                        mb2 = self.grad_update_block.motion_batch(iters - half - 1, net, grad_samples=sup_grad_samples)
-                    net, up_mask, delta_flow = self.grad_update_block.forward_cl(net, inp, corr, flow, head_batch=hb2, grad_samples=sup_grad_samples,
-                                                                                 motion_batch=mb2 if itr > half else None)
-
-                flow = flow + delta_flow
-                if not test_mode and (hb if itr < half else hb2) is not None:
-                    (flows if itr < half else flows2).append(flow)
-                    continue
-                if not want_up:
-                    continue
-                if up_mask is None:
-                    flow_up = upflow8(flow)
-                else:
-                    flow_up = convex_upsample(flow, up_mask, channels_last=True)
-                if not test_mode and itr >= half:
-                    flow_up = _crop_back(flow_up, *crop)
-                flow_predictions.append(flow_up)
-        finally:
-            torch.set_grad_enabled(grad_mode)
-        # the deferred mask head + upsampler of each phase (after the caller's gradient mode is back: the unlabelled pass of the
-        # flow-supervisor step switches it off for the supervisor's half).  A phase that ran without a batch has its predictions in
-        # the list already; the student's come first.
-        if hb is not None and flows:
-            flow_predictions = hb.finish(flows) + flow_predictions
-        if hb2 is not None and flows2:
-            flow_predictions = flow_predictions + [_crop_back(p, *crop) for p in hb2.finish(flows2)]
-
-        if test_mode:
-            return flow, flow_up
-        return flow_predictions
+        return self._two_phase(image1, image2, ci1, ci2, ox, oy, iters, flow_init, test_mode, supervisor_grad, sup_grad_samples)

@@ -2,16 +2,16 @@
 values and state_dict keys as pytorch/core/raft.py:24-144; the loop body differs only in that
 tensors between the lookup, the update block and the upsampler stay channels-last so no
 layout conversion (and no torch.cat / softmax / unfold) runs per iteration.
-"""
-import os
 
+Every forward of the package (RAFT, RAFTGMA, L2L, GMAL2L) is `_Shell._encode`, then one or two calls of `refine`.
+"""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from . import streams
 from .corr import AlternateCorrBlock, CorrBlock
-from .extractor import BasicEncoder, SmallEncoder
+from .extractor import BasicEncoder, SmallEncoder, _prepare_packs
 from .update import BasicUpdateBlock, SmallUpdateBlock, to_channels_last
 from .utils.utils import coords_grid, upflow8
 from .._lib import on_tensor_device
@@ -44,7 +44,133 @@ def convex_upsample(flow, mask, channels_last=False):
     return _ConvexUpsample.apply(flow, mask)
 
 
-class RAFT(nn.Module):
+def normalise(im):
+    """0..255 -> -1..1 (raft.py:89-90)."""
+    return (2 * (im / 255.0) - 1.0).contiguous()
+
+
+def corr_block(args, fmap1, fmap2):
+    """The correlation object `args` asks for (raft.py:104-107)."""
+    if getattr(args, "alternate_corr", False):
+        return AlternateCorrBlock(fmap1, fmap2, radius=args.corr_radius, coords_grad=getattr(args, "alt_coords_grad", False))
+    return CorrBlock(fmap1, fmap2, radius=args.corr_radius)
+
+
+def refine(block, corr_fn, net, inp, flow, iters, attention=None, test_mode=False, grad_samples=None, first_corr=None,
+           motion_iters=None):
+    """One refinement phase: `iters` calls of the update block `block` on one grid with one correlation object.
+    -> (net, flow, flow_up, finish): the state after the phase, the last upsampled flow (test_mode; else None) and finish(), which
+    returns the phase's upsampled predictions -- DEFERRED: in training the mask head and the upsampler of all iterations run as
+    one launch each (update.HeadBatch) when finish() is called, under the gradient mode of that moment.
+
+    The phase carries the FLOW, not coords1 = coords0 + flow (raft.py:121-131): the lookup adds the pixel grid itself, the update
+    block and the upsampler want the flow anyway, so an iteration has one framework op (flow + delta) instead of three.  Same
+    gradient structure: the flow entering an iteration is detached, delta_flow reaches the loss through the prediction.
+    test_mode: only the last iteration's mask convolution and upsampler run (raft.py:141-142 returns that one alone; the
+    reference computes the others and drops them).
+    grad_samples: passed to every update-block call (and to the MotionBatch).
+    first_corr: the correlation features of `flow`, looked up by the caller, who hands `flow` over detached: the first
+    iteration's detach + lookup are the caller's.
+    motion_iters: how many of the iterations (the last ones) write into a update.MotionBatch, whose motion-encoder backward is
+    one launch per layer; None: no MotionBatch."""
+    train = not test_mode
+    hb = block.head_batch(iters, net) if train else None
+    mb = block.motion_batch(motion_iters, net, grad_samples=grad_samples) if train and motion_iters is not None else None
+    flows, ups, flow_up = [], [], None
+    for i in range(iters):
+        cur = mb if mb is not None and i >= iters - motion_iters else None
+        if i == 0 and first_corr is not None:
+            corr = first_corr
+        else:
+            flow = flow.detach()
+            corr = corr_fn(flow, channels_last=True, is_flow=True, **({"out": cur.corr[cur.n]} if cur is not None else {}))
+        want_up = train or i == iters - 1                   # (training: True, the default of need_mask)
+        net, up_mask, delta_flow = block.forward_cl(net, inp, corr, flow, attention, need_mask=want_up, head_batch=hb,
+                                                    grad_samples=grad_samples, motion_batch=cur)
+        flow = flow + delta_flow
+        if hb is not None:
+            flows.append(flow)
+        elif want_up:
+            flow_up = upflow8(flow) if up_mask is None else convex_upsample(flow, up_mask, channels_last=True)
+            ups.append(flow_up)
+    return net, flow, flow_up, lambda: hb.finish(flows) if flows else ups
+
+
+class _Shell(nn.Module):
+    """What the four models share around their phases: the reference's helper methods and the encode step.  A subclass has
+    fnet, cnet, hidden_dim, context_dim and args."""
+
+    def freeze_bn(self):
+        for m in self.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+
+    def initialize_flow(self, img):
+        """coords0 == coords1 == pixel grid at 1/8 resolution; flow = coords1 - coords0 (raft.py:63-70)."""
+        N, C, H, W = img.shape
+        c = coords_grid(N, H // 8, W // 8, device=img.device)
+        return c, c.clone()
+
+    @on_tensor_device
+    def upsample_flow(self, flow, mask):
+        """[N,2,H,W], [N,576,H,W] -> [N,2,8H,8W] convex combination (raft.py:72-83)."""
+        return convex_upsample(flow, mask)
+
+    # (autocast off, also a caller's: args.mixed_precision is accepted and without effect, see utils.warn_mixed_precision --
+    #  fp32 storage everywhere, at full speed)
+    def _features(self, a, b):
+        with autocast("cuda", enabled=False):
+            f1, f2 = self.fnet([a, b])
+        return f1.float(), f2.float()
+
+    def _corr_block(self, fmap1, fmap2):
+        return corr_block(self.args, fmap1, fmap2)
+
+    def _context_split(self, img):
+        with autocast("cuda", enabled=False):
+            cnet = self.cnet(img)
+        return torch.split(cnet.float(), [self.hidden_dim, self.context_dim], dim=1)
+
+    def _context(self, img):
+        """-> (net, inp, attention): hidden state and context features, channels-last as the loop keeps them; no attention."""
+        net, inp = self._context_split(img)
+        return to_channels_last(torch.tanh(net)), to_channels_last(torch.relu(inp)), None
+
+    def _encode(self, image1, image2, flow_init, overlap=True, side_work=None):
+        """Frames the calling `forward` has put through `normalise` -> corr_fn, (net, inp, attention), flow, side.  The context
+        encoder reads image1 only: with `overlap` and core/streams.py on it runs on the second stream beside the feature encoder
+        and the volume build (`_corr_block`: RAFT's follows args.alternate_corr, the GMA family's does not).  side_work (L2L,
+        GMAL2L): further work for that stream, issued behind the context, which alone the caller's stream then waits for; `side`
+        is what it returned (None where there is no second stream).  flow: flow_init, or zeros on the 1/8 grid."""
+        overlap = overlap and streams.OVERLAP and image1.is_cuda
+        side = ctx_done = None
+        if overlap:
+            if side_work is not None:       # (the packed weights both streams read are built on this one first)
+                _prepare_packs(self.fnet)
+                _prepare_packs(self.cnet)
+            with torch.cuda.stream(streams.fork(image1.device)):
+                state = self._context(image1)
+                if side_work is not None:
+                    ctx_done = streams.mark(image1.device)
+                    side = side_work()
+        corr_fn = self._corr_block(*self._features(image1, image2))
+        if overlap:
+            streams.join(image1.device, *state, event=ctx_done)
+        else:
+            state = self._context(image1)
+        B, _, Hi, Wi = image1.shape
+        flow = flow_init.float() if flow_init is not None else torch.zeros(B, 2, Hi // 8, Wi // 8, device=image1.device)
+        return corr_fn, state, flow, side
+
+    def _single_phase(self, image1, image2, iters, flow_init, test_mode, **encode):
+        """Frames the calling `forward` has put through `normalise` -> encode, one phase of `update_block` over all iterations,
+        finish: the forward of RAFT and RAFTGMA, and of the L2L models in test mode."""
+        corr_fn, (net, inp, attention), flow, _ = self._encode(image1, image2, flow_init, **encode)
+        _, flow, flow_up, finish = refine(self.update_block, corr_fn, net, inp, flow, iters, attention, test_mode, motion_iters=iters)
+        return (flow, flow_up) if test_mode else finish()
+
+
+class RAFT(_Shell):
     def __init__(self, args):
         super().__init__()
         self.args = args
@@ -73,91 +199,6 @@ class RAFT(nn.Module):
             self.cnet.out_channels_last = True   # the context features reach the update block channels_last (extractor._Encoder.forward)
             self.update_block = BasicUpdateBlock(self.args, hidden_dim=hdim)
 
-    def freeze_bn(self):
-        for m in self.modules():
-            if isinstance(m, nn.BatchNorm2d):
-                m.eval()
-
-    def initialize_flow(self, img):
-        """coords0 == coords1 == pixel grid at 1/8 resolution; flow = coords1 - coords0 (raft.py:63-70)."""
-        N, C, H, W = img.shape
-        c = coords_grid(N, H // 8, W // 8, device=img.device)
-        return c, c.clone()
-
-    @on_tensor_device
-    def upsample_flow(self, flow, mask):
-        """[N,2,H,W], [N,576,H,W] -> [N,2,8H,8W] convex combination (raft.py:72-83)."""
-        return convex_upsample(flow, mask)
-
     @on_tensor_device
     def forward(self, image1, image2, iters=12, flow_init=None, upsample=True, test_mode=False):
-        image1 = (2 * (image1 / 255.0) - 1.0).contiguous()
-        image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
-        hdim, cdim = self.hidden_dim, self.context_dim
-        amp = False          # args.mixed_precision: no autocast here, see utils.warn_mixed_precision (fp32 storage everywhere, at full speed)
-
-        def context():
-            with autocast("cuda", enabled=amp):
-                cnet = self.cnet(image1)
-            net, inp = torch.split(cnet.float(), [hdim, cdim], dim=1)
-            # hidden state stays channels-last in the loop
-            return to_channels_last(torch.tanh(net)), to_channels_last(torch.relu(inp))
-
-        # the context encoder reads image1 only: on the second stream beside the feature encoder and the volume build (core/streams.py)
-        overlap = streams.OVERLAP and image1.is_cuda
-        if overlap:
-            with torch.cuda.stream(streams.fork(image1.device)):
-                net, inp = context()
-        with autocast("cuda", enabled=amp):
-            fmap1, fmap2 = self.fnet([image1, image2])
-        fmap1, fmap2 = fmap1.float(), fmap2.float()
-        if self.args.alternate_corr:
-            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, coords_grad=getattr(self.args, "alt_coords_grad", False))
-        else:
-            corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
-        if overlap:
-            streams.join(image1.device, net, inp)
-        else:
-            net, inp = context()
-
-        # The loop carries the FLOW, not coords1 = coords0 + flow (raft.py:121-131): the lookup adds the pixel grid itself,
-        # the update block and the upsampler want the flow anyway, so an iteration has one framework op (flow + delta)
-        # instead of three.  Same gradient structure: the flow entering an iteration is detached, delta_flow reaches the
-        # loss through the upsampled prediction.
-        B, _, Hi, Wi = image1.shape
-        if flow_init is not None:
-            flow = flow_init.float()
-        else:
-            flow = torch.zeros(B, 2, Hi // 8, Wi // 8, device=image1.device)
-
-        flow_predictions = []
-        flow_up = None
-        # training: the mask head and the upsampler of all iterations run as one launch each after the loop (update.HeadBatch)
-        hb = self.update_block.head_batch(iters, net) if not test_mode else None
-        # ... and the motion encoder's backward of all iterations likewise (update.MotionBatch: the lookups write into its slots)
-        mb = self.update_block.motion_batch(iters, net) if not test_mode else None
-        flows = []
-        for itr in range(iters):
-            flow = flow.detach()
-            corr = corr_fn(flow, channels_last=True, is_flow=True, **({"out": mb.corr[mb.n]} if mb is not None else {}))
-            # test_mode returns only the last upsampled flow (raft.py:141-142): the mask convolution and the upsampler of
-            # the other iterations are skipped -- same outputs, the reference computes them and drops them (raft.py:134-139)
-            want_up = not test_mode or itr == iters - 1
-            net, up_mask, delta_flow = self.update_block.forward_cl(net, inp, corr, flow, need_mask=want_up, head_batch=hb, motion_batch=mb)
-            flow = flow + delta_flow
-            if hb is not None:
-                flows.append(flow)
-                continue
-            if not want_up:
-                continue
-            if up_mask is None:
-                flow_up = upflow8(flow)
-            else:
-                flow_up = convex_upsample(flow, up_mask, channels_last=True)
-            flow_predictions.append(flow_up)
-
-        if hb is not None:
-            flow_predictions = hb.finish(flows)
-        if test_mode:
-            return flow, flow_up
-        return flow_predictions
+        return self._single_phase(normalise(image1), normalise(image2), iters, flow_init, test_mode)

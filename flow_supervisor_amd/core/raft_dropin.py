@@ -14,8 +14,7 @@ gradients to the package shell's.
 import torch
 
 from .._lib import on_tensor_device
-from .corr import AlternateCorrBlock, CorrBlock
-from .raft import RAFT
+from .raft import RAFT, corr_block
 from .utils.utils import coords_grid, upflow8
 
 
@@ -33,10 +32,7 @@ class ReferenceShapedRAFT(RAFT):
         image2 = (2 * (image2 / 255.0) - 1.0).contiguous()
         fmap1, fmap2 = self.fnet([image1, image2])                       # raft.py:98-100
         fmap1, fmap2 = fmap1.float(), fmap2.float()
-        if self.args.alternate_corr:                                     # raft.py:104-107
-            corr_fn = AlternateCorrBlock(fmap1, fmap2, radius=self.args.corr_radius, coords_grad=getattr(self.args, "alt_coords_grad", False))
-        else:
-            corr_fn = CorrBlock(fmap1, fmap2, radius=self.args.corr_radius)
+        corr_fn = corr_block(self.args, fmap1, fmap2)                    # raft.py:104-107
         cnet = self.cnet(image1)                                         # raft.py:110-114
         net, inp = torch.split(cnet, [self.hidden_dim, self.context_dim], dim=1)
         net, inp = torch.tanh(net), torch.relu(inp)

@@ -14,5 +14,6 @@ Layout mirrors the reference's PyTorch tree so it drops in:
                                                                           (the same two files: selfsup and 'brox')
     flow_supervisor_amd.augment        UnsupAugmentor, apply, as_step_input, add_noise
                                                                           (pytorch/raft_utils/augmentor.py:496-657)
+                                       FlowAugmentor, SparseFlowAugmentor, apply_supervised      (augmentor.py:39-330)
 The compute lives in csrc/*.hip behind the C ABI of include/fsraft.h (libfsraft.so).
 """

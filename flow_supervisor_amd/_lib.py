@@ -171,6 +171,9 @@ SIGNATURES = {
     "fsraft_augment_scratch_bytes": [c_int, c_int, c_int, c_int, c_int],
     "fsraft_augment": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, POINTER(AugParams), c_int, c_int, c_int, c_int,
                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_augment_sup_scratch_bytes": [c_int, c_int, c_int],
+    "fsraft_augment_sup": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(AugParams), c_int, c_int,
+                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, _S],
     "fsraft_inorm_relu_cl_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int, c_int, _S],
     "fsraft_inorm_relu_cl_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                  c_int, c_int, _S],

@@ -1811,28 +1811,34 @@ def selfsup(teacher, teacher_mask, student, student_back, mode, norm=1.0, crop=N
 AUG_DTYPES = {torch.uint8: 0, torch.float32: 1}      # FSRAFT_AUG_U8 / FSRAFT_AUG_F32 of include/fsraft.h
 
 
-def augment(image1, image2, flow, valid, params, frame_hw, crop_hw):
-    """fsraft_augment: image1, image2 [B,Hs,Ws,3] interleaved, uint8 or fp32 in [0, 1]; flow [B,Hs,Ws,2] and valid [B,Hs,Ws] (or
-    None: ones) fp32; params: a ctypes array of B _lib.AugParams (host memory, read before the launches); frame_hw = (Hf, Wf),
-    crop_hw = (h, w).  Returns (frame1, frame2, frame_flow, frame_valid, crop1, crop2, crop_flow, crop_valid), planar fp32."""
+def _augment_sources(what, image1, image2, flow, valid, params):
+    """The checks `augment` and `augment_sup` share -> (B, Hs, Ws)."""
     L.require_cuda_f32(flow, valid)
     for t in (image1, image2):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
             raise RuntimeError("fsraft ops need CUDA (ROCm) tensors; the hot path has no CPU implementation")
     if image1.dtype not in AUG_DTYPES or image2.dtype != image1.dtype:
-        raise RuntimeError(f"augment: images are uint8 or fp32, both the same, got {image1.dtype} and {image2.dtype}")
+        raise RuntimeError(f"{what}: images are uint8 or fp32, both the same, got {image1.dtype} and {image2.dtype}")
     if image1.dim() != 4 or image1.shape[3] != 3:
-        raise RuntimeError(f"augment: images are [B,Hs,Ws,3], got {tuple(image1.shape)}")
+        raise RuntimeError(f"{what}: images are [B,Hs,Ws,3], got {tuple(image1.shape)}")
     B, Hs, Ws, _ = image1.shape
     if image2.shape != image1.shape or flow.shape != (B, Hs, Ws, 2) or (valid is not None and valid.shape != (B, Hs, Ws)):
-        raise RuntimeError(f"augment: image1 {tuple(image1.shape)}, image2 {tuple(image2.shape)}, flow {tuple(flow.shape)}, "
+        raise RuntimeError(f"{what}: image1 {tuple(image1.shape)}, image2 {tuple(image2.shape)}, flow {tuple(flow.shape)}, "
                            f"valid {None if valid is None else tuple(valid.shape)}")
     if any(t.device != flow.device for t in (image1, image2)):
         raise RuntimeError("fsraft ops need all tensors on one device")
     if not all(t.is_contiguous() for t in (image1, image2, flow, valid) if t is not None):
-        raise RuntimeError("augment: the sources are contiguous")
+        raise RuntimeError(f"{what}: the sources are contiguous")
     if len(params) != B:
-        raise RuntimeError(f"augment: {B} samples and {len(params)} parameter sets")
+        raise RuntimeError(f"{what}: {B} samples and {len(params)} parameter sets")
+    return B, Hs, Ws
+
+
+def augment(image1, image2, flow, valid, params, frame_hw, crop_hw):
+    """fsraft_augment: image1, image2 [B,Hs,Ws,3] interleaved, uint8 or fp32 in [0, 1]; flow [B,Hs,Ws,2] and valid [B,Hs,Ws] (or
+    None: ones) fp32; params: a ctypes array of B _lib.AugParams (host memory, read before the launches); frame_hw = (Hf, Wf),
+    crop_hw = (h, w).  Returns (frame1, frame2, frame_flow, frame_valid, crop1, crop2, crop_flow, crop_valid), planar fp32."""
+    B, Hs, Ws = _augment_sources("augment", image1, image2, flow, valid, params)
     (Hf, Wf), (h, w) = frame_hw, crop_hw
     n = _lib().fsraft_augment_scratch_bytes(B, Hf, Wf, h, w)
     if n == 1:
@@ -1844,4 +1850,27 @@ def augment(image1, image2, flow, valid, params, frame_hw, crop_hw):
     scratch = torch.empty(n // 8, device=dev, dtype=torch.float64)
     L.check(_lib().fsraft_augment(L.ptr(image1), L.ptr(image2), AUG_DTYPES[image1.dtype], L.ptr(flow), L.ptr(valid), B, Hs, Ws, params,
                                   Hf, Wf, h, w, *[L.ptr(t) for t in outs], L.ptr(scratch), n, L.stream()), "augment")
+    return outs
+
+
+AUG_FLOW_MODES = {"bilinear": 0, "nearest": 1}       # FSRAFT_AUG_FLOW_BILINEAR / FSRAFT_AUG_FLOW_NEAREST
+
+
+def augment_sup(image1, image2, flow, valid, params, crop_hw, flow_mode):
+    """fsraft_augment_sup (FlowAugmentor / SparseFlowAugmentor: colour, eraser, then resize, flips and crop): sources and params
+    as for `augment`; crop_hw = (h, w); flow_mode 'bilinear' (dense ground truth; valid is ignored, the result all ones) or
+    'nearest' (sparse).  Returns (crop1, crop2, crop_flow, crop_valid), planar fp32, images in [0, 255]."""
+    if flow_mode not in AUG_FLOW_MODES:
+        raise RuntimeError(f"augment_sup: flow_mode is one of {sorted(AUG_FLOW_MODES)}, got {flow_mode!r}")
+    B, Hs, Ws = _augment_sources("augment_sup", image1, image2, flow, valid, params)
+    h, w = crop_hw
+    n = _lib().fsraft_augment_sup_scratch_bytes(B, Hs, Ws)
+    if n == 1:
+        raise RuntimeError(f"libfsraft: augment_sup_scratch_bytes({B}, {Hs}, {Ws}) failed with status 1 (bad argument)")
+    dev = flow.device
+    outs = tuple(torch.empty(B, c, h, w, device=dev, dtype=torch.float32) for c in (3, 3, 2, 1))
+    scratch = torch.empty(n // 8, device=dev, dtype=torch.float64)
+    L.check(_lib().fsraft_augment_sup(L.ptr(image1), L.ptr(image2), AUG_DTYPES[image1.dtype], L.ptr(flow), L.ptr(valid),
+                                      AUG_FLOW_MODES[flow_mode], B, Hs, Ws, params, h, w, *[L.ptr(t) for t in outs], L.ptr(scratch), n,
+                                      L.stream()), "augment_sup")
     return outs

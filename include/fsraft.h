@@ -594,6 +594,45 @@ int fsraft_augment(const void* image1, const void* image2, int dtype, const floa
                    float* frame_valid, float* crop1, float* crop2, float* crop_flow, float* crop_valid, void* scratch,
                    int64_t scratch_bytes, hipStream_t stream);
 
+/* ---- FlowAugmentor / SparseFlowAugmentor applied to a batch (csrc/augment.hip; flow_supervisor_amd/augment.py) -------------
+ * pytorch/raft_utils/augmentor.py:39-188 (dense ground truth) and :191-330 (sparse), in the order of their __call__: colour,
+ * eraser, spatial.  The formulas below are the definition (restated in float64 in tests/_supaugref.py).
+ *
+ * Sources, dtypes and params as for fsraft_augment, with fsraft_aug_params read this way: win_y = win_x = 0; th x tw is the size
+ * of the resized image (resize 0: Hs x Ws); (crop_y, crop_x) is the crop's corner in the flipped resized image, any integer;
+ * rect[r] is in SOURCE coordinates.  th and tw may differ between the samples of a batch.  Outputs are planar, contiguous fp32,
+ * every element written: crop1 / crop2 [B][3][h][w] in [0, 255], crop_flow [B][2][h][w], crop_valid [B][1][h][w].
+ *
+ * Per sample, with x = source / 255 (uint8) or the source (float):
+ * Photometric source: P_i = clip(hue(sat(contrast(x * brightness[i]))), 0, 1) with the colour formulas of fsraft_augment, the
+ * contrast mean being the per-channel mean of the brightness-scaled SOURCE image i (asym 0: over both sources, which the
+ * reference stacks into one image).
+ * Eraser: m2 = the per-channel mean of P_2 over the whole source, before any rectangle; E_2 = m2 inside any rect[r], else P_2;
+ * E_1 = P_1.  An empty rectangle changes nothing.
+ * Spatial: crop pixel (y, x) is pixel ry = vflip ? th-1-(crop_y+y) : crop_y+y, rx = hflip ? tw-1-(crop_x+x) : crop_x+x of E_i
+ * resized to th x tw with TF2 tf.image.resize(BILINEAR) (half-pixel centres, no antialias; the taps and weights of
+ * fsraft_augment, along x within the two rows, then along y; resize 0: the pixel itself), times 255.
+ * Flow: FSRAFT_AUG_FLOW_BILINEAR the same bilinear taps on the flow, FSRAFT_AUG_FLOW_NEAREST the nearest-neighbour index of
+ * fsraft_augment on flow and valid; then times (scale_x, scale_y) (resize 0: not at all), times (-1, 1) under hflip and
+ * (1, -1) under vflip.  crop_valid in mode BILINEAR is all ones and a given `valid` is ignored (flow_dataset.py:126).
+ * All index arithmetic in float32.  Nothing of source or resized size is written to memory: the colour step and the rectangle
+ * test are evaluated at each tap.
+ *
+ * Sums are fp64 per workgroup in `scratch` (8-byte aligned, at least fsraft_augment_sup_scratch_bytes, nothing to initialise),
+ * added in workgroup order: no float atomics, bit-identical from run to run.  No allocation, no synchronisation; five launches
+ * per 16 samples (three when none of them has a non-empty rectangle).
+ * FSRAFT_ERR_ARG, before any HIP call, for a null (valid excepted) or misaligned pointer, an unknown dtype or flow_mode, a size
+ * below 1, Hs * Ws * 3, h * w * 3 or th * tw beyond 2^31 - 1, resize 0 with (th, tw) != (Hs, Ws), win_y or win_x != 0, th < h or
+ * tw < w, a crop outside th x tw, a rectangle outside the source, nrect outside 0..2, a flag other than 0 or 1, a non-finite
+ * factor, asym 0 with factors that differ between the two images, or too little scratch. */
+#define FSRAFT_AUG_FLOW_BILINEAR 0   /* FlowAugmentor */
+#define FSRAFT_AUG_FLOW_NEAREST  1   /* SparseFlowAugmentor */
+int fsraft_augment_sup_scratch_bytes(int B, int Hs, int Ws);
+int fsraft_augment_sup(const void* image1, const void* image2, int dtype, const float* flow, const float* valid, int flow_mode,
+                       int B, int Hs, int Ws, const fsraft_aug_params* params, int h, int w,
+                       float* crop1, float* crop2, float* crop_flow, float* crop_valid,
+                       void* scratch, int64_t scratch_bytes, hipStream_t stream);
+
 /* Channels-last ([B][HW][C], C % 4 == 0, C <= 256) variants, for the encoder stages whose convolutions run on
  * fsraft_conv_forward.  sums/sumsq/s1/s2 and dsum_g/dsum_gx: [B * 8][C] partial rows (workgroups spread their atomics over
  * eight rows per sample: thousands of adds on the same C addresses serialise in L2 otherwise; dsum_*: the per-channel sums

@@ -150,6 +150,10 @@ SIGNATURES = {
     "fsraft_flow_metrics_scratch_bytes": [c_int, c_int, c_int],
     "fsraft_flow_metrics": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64,
                             c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_flow_rad_max": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_float, c_void_p, _S],
+    "fsraft_flow_wheel": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_float, c_void_p, c_float, c_int, c_void_p, _S],
+    "fsraft_flow_hsv": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_float, c_int, c_void_p, _S],
+    "fsraft_flow_kitti16": [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, _S],
     "fsraft_range_map_scratch_bytes": [c_int, c_int, c_int],
     "fsraft_range_map": [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, _S],
     "fsraft_census_scratch_bytes": [c_int, c_int, c_int],

@@ -1653,6 +1653,75 @@ def flow_metrics(pred, gt, valid, sample_stats, acc=None, scratch=None):
     return sample_stats
 
 
+# ------------------------------------------------------------------ flow visualisation and submission encoding
+def _flow_view(what, flow, *more):
+    """The checks of flow_metrics for a [B,2,H,W] view (and [B,H,W] companions): device, fp32, unit x stride, shapes."""
+    L.require_cuda_f32(flow, *more)
+    if flow.dim() != 4 or flow.shape[1] != 2 or 0 in flow.shape:
+        raise RuntimeError(f"{what}: flow has shape {tuple(flow.shape)}, not [B,2,H,W]")
+    if flow.shape[-1] > 1 and flow.stride(-1) != 1:
+        raise RuntimeError(f"{what}: flow needs a unit x stride")
+    return flow.shape[0], flow.shape[2], flow.shape[3]
+
+
+def _flow_out(what, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, device=device, dtype=dtype)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise RuntimeError(f"{what}: out must be a contiguous {dtype} {tuple(shape)} tensor on {device}")
+    return out
+
+
+def flow_rad_max(flow, clip=0.0, out=None):
+    """fsraft_flow_rad_max: flow [B,2,H,W] fp32 view with unit x stride -> float[B] on the device, the largest
+    sqrt(u*u + v*v) among each sample's finite pixels (0 without one).  clip > 0 clamps u and v to [0, clip] first (the
+    reference's np.clip(flow_uv, 0, clip_flow): the lower bound is 0).  No host read."""
+    B, H, W = _flow_view("flow_rad_max", flow)
+    out = _flow_out("flow_rad_max", out, (B,), torch.float32, flow.device)
+    L.check(_lib().fsraft_flow_rad_max(L.ptr(flow), *flow.stride()[:3], B, H, W, float(clip), L.ptr(out), L.stream()), "flow_rad_max")
+    return out
+
+
+def flow_colors(flow, rad_max=None, scale=None, clip=0.0, bgr=False, out=None):
+    """fsraft_flow_wheel: the Middlebury wheel colouring, flow [B,2,H,W] -> uint8 [B,H,W,3].  Normalised by rad_max[b] + 1e-5
+    (rad_max: float[B] from flow_rad_max) or by the host scalar `scale` -- exactly one of the two."""
+    B, H, W = _flow_view("flow_colors", flow, rad_max)
+    if (rad_max is None) == (scale is None):
+        raise RuntimeError("flow_colors: give rad_max (a device float[B]) or scale (a host number), not both or neither")
+    if rad_max is not None and (tuple(rad_max.shape) != (B,) or not rad_max.is_contiguous()):
+        raise RuntimeError(f"flow_colors: rad_max must be a contiguous fp32 ({B},) tensor")
+    out = _flow_out("flow_colors", out, (B, H, W, 3), torch.uint8, flow.device)
+    L.check(_lib().fsraft_flow_wheel(L.ptr(flow), *flow.stride()[:3], B, H, W, float(clip), L.ptr(rad_max),
+                                     float(scale) if scale is not None else 0.0, int(bool(bgr)), L.ptr(out), L.stream()), "flow_colors")
+    return out
+
+
+def flow_hsv(flow, rad_max=None, max_mag=0.0, as_uint8=False, out=None):
+    """fsraft_flow_hsv: the HSV coding of util/visualize.py, flow [B,2,H,W] -> fp32 [B,H,W,3] in [0, 1], or uint8 (truncated
+    255 * c) with as_uint8.  max_mag > 0: saturation clamp(rho / max_mag, 0, 1); 0: rho / rad_max[b] (from flow_rad_max)."""
+    B, H, W = _flow_view("flow_hsv", flow, rad_max)
+    if rad_max is not None and (tuple(rad_max.shape) != (B,) or not rad_max.is_contiguous()):
+        raise RuntimeError(f"flow_hsv: rad_max must be a contiguous fp32 ({B},) tensor")
+    out = _flow_out("flow_hsv", out, (B, H, W, 3), torch.uint8 if as_uint8 else torch.float32, flow.device)
+    L.check(_lib().fsraft_flow_hsv(L.ptr(flow), *flow.stride()[:3], B, H, W, L.ptr(rad_max), float(max_mag), int(bool(as_uint8)),
+                                   L.ptr(out), L.stream()), "flow_hsv")
+    return out
+
+
+def flow_kitti16(flow, valid=None, out=None):
+    """fsraft_flow_kitti16: flow [B,2,H,W] (and valid [B,H,W] or None) -> [B,H,W,3] holding the uint16 values
+    (64 u + 2^15, 64 v + 2^15, valid >= 0.5 or 1), truncated and clamped to [0, 65535]: the KITTI PNG's R, G, B.  torch may
+    lack a uint16 dtype, so the tensor is int16 with the same bits: `.cpu().numpy().view(np.uint16)`."""
+    B, H, W = _flow_view("flow_kitti16", flow, valid)
+    if valid is not None and (tuple(valid.shape) != (B, H, W) or (W > 1 and valid.stride(-1) != 1)):
+        raise RuntimeError(f"flow_kitti16: valid {tuple(valid.shape)} must be ({B}, {H}, {W}) with a unit x stride")
+    out = _flow_out("flow_kitti16", out, (B, H, W, 3), torch.int16, flow.device)
+    vs = (valid.stride(0), valid.stride(1)) if valid is not None else (0, 0)
+    L.check(_lib().fsraft_flow_kitti16(L.ptr(flow), *flow.stride()[:3], L.ptr(valid), *vs, B, H, W, L.ptr(out), L.stream()),
+            "flow_kitti16")
+    return out
+
+
 # ------------------------------------------------------------------ unsupervised (SMURF) loss
 def _scratch_f64(fn, what, B, H, W, device):
     n = fn(B, H, W)

@@ -20,3 +20,4 @@ with it off, the default, such a call that wants a gradient raises.
 """
 from .api import (BasicUpdateBlock, CorrBlock, UpsampleConvexWithMask, build_pyramid, calc_all_field,  # noqa: F401
                   same_grad, transpose_volume)
+from .visualize import visualize_flow, visualize_flows  # noqa: F401    util/visualize.py:5-27, 40-42 (HSV flow coding)

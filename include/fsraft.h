@@ -452,6 +452,55 @@ int fsraft_flow_metrics(const float* pred, int64_t pred_bs, int64_t pred_cs, int
                         const float* valid, int64_t valid_bs, int64_t valid_rs, int B, int H, int W,
                         double* sample_stats, double* acc, void* scratch, int64_t scratch_bytes, hipStream_t stream);
 
+/* ---- flow visualisation and submission encoding (a step next to the path; csrc/flow_viz.hip) -----------------------------
+ * What the reference's inference scripts do on the host after `.cpu().numpy()`: the Middlebury colour wheel of
+ * pytorch/core/utils/flow_viz.py, the HSV coding of util/visualize.py:5-27 and the 16-bit KITTI encoding of
+ * pytorch/raft_utils/frame_utils.py:121-125.  flow: a [B][2][H][W] fp32 view, strides in elements, x stride 1, nothing else
+ * assumed (the un-padded view of a padded prediction is read in place); outputs are contiguous, every element written.  All
+ * arithmetic is fp32 with every operation rounded on its own.  No allocation, no synchronisation, no device -> host read;
+ * every launch goes on `stream`, so a call can be captured in a graph.  Bit-identical from run to run, and sample b of a batch
+ * gives the bits it gives alone.  FSRAFT_ERR_ARG, before any HIP call, for a null flow or output, B, H or W below 1, B beyond
+ * 65535, H * W beyond 2^31 - 1, a misaligned pointer and the argument values named below.
+ *
+ * fsraft_flow_rad_max (flow_viz.py:123-128): rad_max[b] = the maximum over the sample's finite pixels (both components
+ * finite) of sqrtf(u*u + v*v); 0 for a sample without one.  clip > 0: u and v are first clamped to [0, clip] -- the LOWER
+ * BOUND 0 IS THE REFERENCE'S QUIRK, np.clip(flow_uv, 0, clip_flow), kept here: negative components vanish (by comparison, as np.clip: a component of -0.0 stays
+ * -0.0, and keeps its end of the wheel).  clip == 0: no clamp.  A negative, NaN or infinite clip is refused.  rad_max (float[B], device) is zeroed by the call itself and then
+ * raised with an atomic maximum on the bit pattern of the non-negative float: a maximum is order-independent.
+ *
+ * fsraft_flow_wheel (flow_viz.py:70-106, 129-132): out uint8 [B][H][W][3], RGB (bgr 1: BGR).  Per pixel, after the same
+ * clamp: den = rad_max[b] + 1e-5f (rad_max non-NULL) or the host scalar `scale` (rad_max NULL; not positive, NaN or infinite
+ * is refused); u' = u / den, v' = v / den, rad = sqrtf(u'*u' + v'*v'); a = atan2f(-v', -u') / pi; fk = (a + 1) / 2 * 54;
+ * k0 = floor(fk), f = fk - k0, k0 then clamped to [0, 54], k1 = k0 + 1 with 55 wrapping to 0; per channel
+ * col = (1 - f) * wheel[k0] / 255 + f * wheel[k1] / 255; rad <= 1: col = 1 - rad * (1 - col), else col = 0.75 * col;
+ * out = floor(255 * col).  wheel is the 55-entry table of make_colorwheel (RY 15, YG 6, GC 4, CB 11, BM 13, MR 6).  With
+ * scale 1 this is flow_uv_to_colors(u, v), the only way into the 0.75 branch.  A pixel with a non-finite component is painted
+ * (0, 0, 0) and takes no part in the maximum; the reference has no rule there (a NaN poisons np.max and the whole picture).
+ * The reference evaluates everything from the table lookup on in float64; a value that lands within rounding of an integer
+ * may come out one level off (tests/test_flow_viz_gpu.py bounds how many).
+ *
+ * fsraft_flow_hsv (util/visualize.py:5-27): rho = sqrtf(x*x + y*y); phi = atan2f(y, x), plus 2 pi where negative;
+ * max_mag > 0: s = clamp(rho / max_mag, 0, 1); max_mag == 0: s = rho / rad_max[b] (from fsraft_flow_rad_max with clip 0; a
+ * maximum of 0 is replaced by 1; rad_max NULL is refused); a negative, NaN or infinite max_mag is refused.  h = phi / (2 pi),
+ * v = 1, and RGB as tf.image.hsv_to_rgb has it: d_r = clamp(|6h - 3| - 1), d_g = clamp(2 - |6h - 2|), d_b = clamp(2 - |6h - 4|),
+ * each to [0, 1], c = ((d - 1) * s + 1) * v.  out: fp32 [B][H][W][3] in [0, 1] (out_u8 0) or uint8, (uint8)(255 * c)
+ * truncated as extract_flow.py:154 does (out_u8 1).  A pixel with a non-finite component is (0, 0, 0).  TensorFlow exists on
+ * no machine this runs on: the formula is restated from its source, and parity with TensorFlow is unpinned.
+ *
+ * fsraft_flow_kitti16 (frame_utils.py:122-124): out uint16 [B][H][W][3] = (64 * u + 32768, 64 * v + 32768, valid) in fp32,
+ * truncated toward zero and clamped to [0, 65535] (NaN: 0); the reference's astype(np.uint16) wraps or is undefined from
+ * |flow| >= 512 on.  The third channel is 1, or valid >= 0.5 from a [B][H][W] view with unit x stride (NULL: all ones).
+ * The order (u, v, valid) is the file's R, G, B. */
+int fsraft_flow_rad_max(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs, int B, int H, int W,
+                        float clip, float* rad_max, hipStream_t stream);
+int fsraft_flow_wheel(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs, int B, int H, int W,
+                      float clip, const float* rad_max, float scale, int bgr, uint8_t* out, hipStream_t stream);
+int fsraft_flow_hsv(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs, int B, int H, int W,
+                    const float* rad_max, float max_mag, int out_u8, void* out, hipStream_t stream);
+int fsraft_flow_kitti16(const float* flow, int64_t flow_bs, int64_t flow_cs, int64_t flow_rs,
+                        const float* valid, int64_t valid_bs, int64_t valid_rs, int B, int H, int W, uint16_t* out,
+                        hipStream_t stream);
+
 /* ---- unsupervised (SMURF) loss (a step next to the path: raft/unsup_loss.py UnsupervisedLoss over
  * raft/smurf_models/smurf_utils.py: compute_range_map, census_loss, first/second_order_smoothness_loss) -------------------
  * PyTorch layout: images [B][3][.][.] in [0,1], flows [B][2][H][W] with channel 0 = x (the reference's tf.reverse to

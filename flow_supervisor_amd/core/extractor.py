@@ -1,16 +1,19 @@
 """Feature / context encoders.  Module and parameter names are those of pytorch/core/extractor.py, so reference
 checkpoints load (state_dict keys ``conv1``, ``norm1``, ``layer{1,2,3}.{0,1}.conv{1,2,3}``, ``...downsample.{0,1}``,
 ``conv2``).  What runs where, for an fp32 CUDA input outside autocast whose norms are non-affine InstanceNorm or BatchNorm on
-running statistics (_norm_kind):
+running statistics (_norm_kind), or affine BatchNorm in training mode (_train_bn_ok):
   * the 7x7 stride-2 stem on csrc/stem.hip (_StemFn), channels_last from there on;
   * stride-1 1x1 / 3x3 convolutions on the implicit-GEMM kernels (_ConvCL), from weight images packed once per parameter
     version (_prepare_packs);
   * the two strided convolutions of a stride-2 residual unit on the same kernels over a space-to-depth input (_StridedPairFn);
-  * norm + ReLU (+ the unit's add and outer ReLU) on csrc/norm_cl.hip (_InstNormReluCL, _FrozenBNReluCL).
+  * norm + ReLU (+ the unit's add and outer ReLU) on csrc/norm_cl.hip (_InstNormReluCL, _FrozenBNReluCL) and, for BatchNorm
+    on batch statistics, csrc/norm_bn.hip (_TrainBNReluCL), which also moves the running statistics.
 MIOpen, on NCHW tensors behind a layout copy, is what these do not cover: stride-2 units at odd sizes, channel counts that are
-no multiple of four, the stem at other shapes.  Other norms (GroupNorm, training-mode BatchNorm, none), autocast and CPU
-tensors run the framework's modules throughout, as does FSRAFT_ENCODER_CL=0 with the norm + ReLU on the NCHW kernels of
-csrc/norm.hip.  The switches STATS_IN_EPILOGUE, STEM_KERNEL, S2D_UNITS and S2D_EMIT turn single routes off.
+no multiple of four, the stem at other shapes.  Other norms (GroupNorm, BatchNorm without affine parameters or running
+statistics or with momentum=None, none), autocast and CPU tensors run the framework's modules throughout, as does
+FSRAFT_ENCODER_CL=0 with the norm + ReLU on the NCHW kernels of csrc/norm.hip -- which have no training-mode BatchNorm: that
+one is the framework's module wherever the chain is NCHW or the channels-last kernels do not take the channel count.  The
+switches STATS_IN_EPILOGUE, STEM_KERNEL, S2D_UNITS, S2D_EMIT and TRAIN_BN turn single routes off.
 """
 import os
 from collections import namedtuple
@@ -189,6 +192,36 @@ class _FrozenBNReluCL(torch.autograd.Function):
         dweight, dbias, dcbias = ops.bn_fold_bwd(part, rs, rmc, scale, ctx.has_cbias)
         dx, dres = _cl_norm_leave(ctx, dx, dres)
         return dx, dcbias, dweight, dbias, None, None, None, None, dres, None, None
+
+
+class _TrainBNReluCL(torch.autograd.Function):
+    """relu?(batch_norm(x + cbias)) of an nn.BatchNorm2d in training mode (_train_bn_ok) for channels_last tensors, on
+    csrc/norm_bn.hip; `res` / `link` / `s2d` as in _InstNormReluCL.  The forward moves the module's running statistics and
+    counts the batch, on the device (capturable), with or without a graph.  cbias (the bias the convolution in front ran
+    without) only enters the running mean; its gradient is exactly zero and None is returned for it."""
+
+    @staticmethod
+    def forward(ctx, x, cbias, weight, bias, norm, relu, res=None, link=None, s2d=False):
+        x, res = _cl_norm_enter(ctx, x, res, link, s2d)
+        if x.shape[0] * x.shape[2] * x.shape[3] < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.shape}")
+        rm, rv = norm.running_mean, norm.running_var
+        fp32 = rm.dtype == torch.float32 and rv.dtype == torch.float32
+        m, v = (rm, rv) if fp32 else (rm.float(), rv.float())
+        y, stats = ops.bnorm_cl_fwd(x, res, weight, bias, cbias, m, v, norm.momentum, norm.eps, relu, ctx.s2w)
+        if not fp32:
+            rm.copy_(m), rv.copy_(v)
+        norm.num_batches_tracked.add_(1)
+        ctx.save_for_backward(x, stats, y if res is not None else None)
+        ctx.relu = relu
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, stats, out = ctx.saved_tensors
+        dx, dres, dweight, dbias = ops.bnorm_cl_bwd(_as_cl(g), x, stats, out, ctx.relu, ctx.s2w)
+        dx, dres = _cl_norm_leave(ctx, dx, dres)
+        return dx, None, dweight, dbias, None, None, dres, None, None
 
 
 # GEMM-ready images of one weight (ops.pack_weight modes): fwd = mode 0 and dgrad = mode 1 in fp32, *_split = modes 10 / 11 for
@@ -379,6 +412,7 @@ def _stem_ok(conv, x):
 STATS_IN_EPILOGUE = True   # False: every InstanceNorm runs its own statistics pass
 STEM_KERNEL = True         # False: the 7x7 stride-2 stem as a MIOpen call
 S2D_UNITS = True           # False: the stride-2 units fall back to MIOpen behind layout hops (the path odd-sized inputs take)
+TRAIN_BN = True            # False: a training-mode BatchNorm keeps the whole encoder on the framework's NCHW modules
 
 
 class _NormSums:
@@ -526,15 +560,31 @@ def _norm_kind(norm):
     return None
 
 
+def _train_bn_ok(norm):
+    """An affine BatchNorm2d in training mode that tracks running statistics with a float momentum: what csrc/norm_bn.hip
+    covers on channels_last tensors (_TrainBNReluCL).  momentum=None, the cumulative average, would need num_batches_tracked
+    on the host, so it stays the framework's."""
+    return (isinstance(norm, nn.BatchNorm2d) and norm.training and norm.affine and norm.track_running_stats
+            and isinstance(norm.momentum, float))
+
+
+def _covered(norm):
+    """Does a fused norm + ReLU kernel cover `norm` on the channels_last path?"""
+    return _norm_kind(norm) is not None or (TRAIN_BN and _train_bn_ok(norm))
+
+
 def _norm_act(norm, y, cbias, relu, res=None, link=None, sums=None, s2d=False, cl=True):
     """relu?(norm(y + cbias)), or relu(res + that), for the output y of a convolution that ran without its bias cbias (or
-    None) and a norm of a kind _norm_kind names.  cl: on the channels_last kernels (where they take y's channel count),
+    None) and a norm of a kind _norm_kind names, or a training-mode BatchNorm (_train_bn_ok) on the channels_last kernels.
+    cl: on the channels_last kernels (where they take y's channel count),
     which fuse the residual and take `link` (the unit's _ResLink), `sums` (the convolution's _NormSums) and `s2d` (see _S2D);
     else on the NCHW ones.  An InstanceNorm removes a per-channel constant again, so cbias is dropped there."""
     kind = _norm_kind(norm)
+    cl = cl and _cl_channels_ok(y.shape[1])
+    if kind is None and cl and _covered(norm):       # training-mode BatchNorm: channels_last kernels only
+        return _TrainBNReluCL.apply(y, cbias, norm.weight, norm.bias, norm, relu, res, link, s2d)
     if kind is None:
         raise RuntimeError(f"no fsraft norm kernel covers {norm!r}")
-    cl = cl and _cl_channels_ok(y.shape[1])
     assert cl or not s2d, "space-to-depth output is a feature of the fused channels_last norm kernels"
     if kind == "instance":
         if cl:
@@ -569,8 +619,11 @@ def _conv_norm(conv, norm, x, relu, to_cl=False, res=None, link=None, res_link=N
         mean subtraction: same output (to rounding), one bias-add kernel less forward and one [N,H,W] reduction less
         backward.  The bias then receives no gradient (mathematically it is exactly zero; parallel.FlatGradients keeps a
         zero for it, so the optimizer treats it as the reference does);
-      * BatchNorm2d using running statistics (context encoder after freeze_bn, or eval mode): the bias joins the shift.
-    Everything else (training-mode BatchNorm, GroupNorm, autocast dtypes, CPU) is the framework's own modules.
+      * BatchNorm2d using running statistics (context encoder after freeze_bn, or eval mode): the bias joins the shift;
+      * BatchNorm2d in training mode (_train_bn_ok, switch TRAIN_BN) on a channels_last chain: csrc/norm_bn.hip.  The bias
+        joins the running mean and, as in front of an InstanceNorm, receives no gradient.  On an NCHW chain it is the
+        framework's module.
+    Everything else (GroupNorm, autocast dtypes, CPU) is the framework's own modules.
     A channels_last input (or to_cl) keeps the chain channels_last: the [N][HW][C] twins of the norm kernels are used, and
     they convert the convolution's output if the library handed back NCHW.  link / res_link: the unit's _ResLink, for its
     first convolution / for the norm that fuses the shortcut `res`."""
@@ -580,6 +633,16 @@ def _conv_norm(conv, norm, x, relu, to_cl=False, res=None, link=None, res_link=N
         sums = _NormSums() if (kind == "instance" and cl) else None
         y = _conv(conv, x, None, link, stem_cl=to_cl, sums=sums)
         return _norm_act(norm, y, conv.bias, relu, res, res_link, sums, s2d, cl)
+    if (kind is None and _covered(norm) and x.is_cuda and x.dtype == torch.float32 and not torch.is_autocast_enabled()
+            and (to_cl or _is_cl(x))):
+        # training-mode BatchNorm on a channels_last chain: the batch mean removes the bias from the output, the kernel adds it to
+        # the running mean; without a kernel for the channel count, the framework's module on conv(x) with its bias
+        if _cl_channels_ok(conv.out_channels):
+            return _norm_act(norm, _conv(conv, x, None, link, stem_cl=to_cl), conv.bias, relu, res, res_link, None, s2d)
+        assert not s2d, "space-to-depth output is a feature of the fused channels_last norm kernels"
+        y = norm(_conv(conv, x, conv.bias))
+        y = F.relu(y, inplace=True) if relu else y
+        return y if res is None else F.relu(res + y)
     assert not s2d, "space-to-depth output is a feature of the fused channels_last norm kernels"
     if kind == "instance" and conv.bias is not None:        # (as above: the bias changes nothing)
         y = F.conv2d(x, conv.weight, None, conv.stride, conv.padding, conv.dilation, conv.groups)
@@ -647,11 +710,11 @@ class _Block(nn.Module):
             y = _conv_norm(getattr(self, f"conv{i}"), getattr(self, f"norm{i}"), y, True, to_cl=cl, link=link if i == 1 else None)
         # last convolution of the unit: relu(x + relu(norm(conv(y)))), the add and outer ReLU fused into the norm kernel
         last, norm = getattr(self, f"conv{self.n}"), getattr(self, f"norm{self.n}")
-        # (the norm's kind decides, not its class: _conv_norm asserts on s2d for a norm without a kind, a training-mode
-        #  BatchNorm say, so a unit in front of a stride-2 unit emits only what its own norm kernel can write)
+        # (whether a kernel covers the norm decides, not its class: _conv_norm asserts on s2d for a norm without one, a
+        #  GroupNorm say, so a unit in front of a stride-2 unit emits only what its own norm kernel can write)
         emit = bool(cl and S2D_EMIT and emit_for is not None and self.downsample is None and _is_cl(y)
                     and _cl_channels_ok(last.out_channels) and _pair_ok(emit_for, last.out_channels, y.shape[2], y.shape[3])
-                    and _norm_kind(norm) is not None)
+                    and _covered(norm))
         out = _conv_norm(last, norm, y, True, to_cl=cl, res=x, res_link=link, s2d=emit)
         return _S2D(out) if emit else out
 
@@ -676,11 +739,12 @@ class BottleneckBlock(_Block):
 
 def _channels_last_ok(enc, x):
     """Channels_last encoder path: fp32 CUDA, no autocast, norms that the fused channels_last kernels cover (non-affine
-    InstanceNorm, BatchNorm on running statistics).  FSRAFT_ENCODER_CL=0 keeps the encoder NCHW on MIOpen throughout."""
+    InstanceNorm, BatchNorm on running statistics, training-mode BatchNorm while TRAIN_BN).  FSRAFT_ENCODER_CL=0 keeps the
+    encoder NCHW on MIOpen throughout."""
     mode = int(os.environ.get("FSRAFT_ENCODER_CL", "1"))
     if mode == 0 or not (x.is_cuda and x.dtype == torch.float32) or torch.is_autocast_enabled():
         return 0
-    return mode if _norm_kind(enc.norm1) is not None else 0
+    return mode if _covered(enc.norm1) else 0
 
 
 class _Encoder(nn.Module):

@@ -1581,6 +1581,37 @@ def inorm_relu_cl_bwd(g, x, stats, out, relu, s2w=0):
     return dx, dres
 
 
+BN_PARTIAL_ROWS = 64       # FSRAFT_BN_PARTIAL_ROWS: rows of the training-mode BatchNorm kernels' partial column sums (norm_bn.hip)
+
+
+def bnorm_cl_fwd(x, res, weight, bias, cbias, running_mean, running_var, momentum, eps, relu, s2w=0):
+    """Training-mode BatchNorm2d: relu?(batch_norm(x + cbias)) on the batch's own statistics, or relu(res + that) with the
+    shortcut `res` -> (y, stats [4, C] = mean, rstd, scale, shift).  cbias: the bias the convolution in front ran without (or
+    None); running_mean / running_var (fp32, both or None) are updated in place."""
+    N, C, H, W = x.shape
+    y = _norm_cl_out(x, s2w)
+    stats = torch.empty(4, C, device=x.device, dtype=torch.float32)
+    acc = zeros(2, BN_PARTIAL_ROWS, C, device=x.device)
+    L.check(_lib().fsraft_bnorm_cl_fwd(L.ptr(x), L.ptr(res), L.ptr(weight.detach().float().contiguous()),
+                                       L.ptr(bias.detach().float().contiguous()),
+                                       L.ptr(cbias.detach().float().contiguous()) if cbias is not None else None,
+                                       L.ptr(running_mean), L.ptr(running_var), float(momentum), float(eps), L.ptr(acc), L.ptr(y),
+                                       L.ptr(stats), N, H * W, C, int(relu), s2w, L.stream()), "bnorm_cl_fwd")
+    return y, stats
+
+
+def bnorm_cl_bwd(g, x, stats, out, relu, s2w=0):
+    """out: the forward's result when it had a shortcut, else None -> (dx, dres or None, dweight, dbias)."""
+    N, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if out is not None else None
+    dpar = torch.empty(2, C, device=x.device, dtype=torch.float32)
+    acc = zeros(2, BN_PARTIAL_ROWS, C, device=x.device)
+    L.check(_lib().fsraft_bnorm_cl_bwd(L.ptr(g), L.ptr(x), L.ptr(stats), L.ptr(out), L.ptr(acc), L.ptr(dx), L.ptr(dres), L.ptr(dpar[0]),
+                                       L.ptr(dpar[1]), N, H * W, C, int(relu), s2w, L.stream()), "bnorm_cl_bwd")
+    return dx, dres, dpar[0], dpar[1]
+
+
 def bn_fold(weight, bias, rm, rv, cbias, eps):
     """A BatchNorm on running statistics behind a convolution that ran without its bias `cbias` (or None), as
     y = x * scale + shift -> (scale, shift, rs = rsqrt(rv + eps), rmc = rm - cbias): the rows of one [4, C] buffer, one launch."""

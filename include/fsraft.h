@@ -713,7 +713,25 @@ int fsraft_bn_fold(const float* weight, const float* bias, const float* rm, cons
 int fsraft_bn_fold_bwd(const float* part, int R, int C, const float* rs, const float* rmc, const float* scale, float* dweight,
                        float* dbias, float* dcbias, hipStream_t stream);
 
-/* ---- the encoders' stem (next-row f3) ---------------------------------------------------
+/* Training-mode BatchNorm2d on the same channels-last layout (csrc/norm_bn.hip): torch.nn.BatchNorm2d in training mode behind
+ * pytorch/core/extractor.py:13-57, 118-170 (the context encoder of pytorch/core/raft.py:55 while its trainer has not called
+ * freeze_bn).  With n = B * HW: mean = sum x / n, var = max(sum x^2 / n - mean^2, 0) (biased), rstd = rsqrt(var + eps),
+ * scale = weight * rstd, shift = bias - mean * scale, t = fma(x, scale, shift), y = relu?(t) or relu(res + relu?(t));
+ * stats [4][C] = (mean, rstd, scale, shift) out.  running_mean / running_var (both or neither) are updated in place:
+ * rm = (1 - momentum) rm + momentum (mean + cbias), rv = (1 - momentum) rv + momentum var n / (n - 1); cbias (nullable) is the
+ * bias of the convolution in front, which ran without it: y does not depend on it, the running mean does.
+ * Backward: g' = g [out > 0] (with a shortcut) [t > 0] (with relu), t recomputed by the forward's fma; xhat = (x - mean) rstd,
+ * S1 = sum g', S2 = sum g' xhat over all n; dx = scale (g' - S1 / n - xhat S2 / n), dweight = S2, dbias = S1, dres = g [out > 0].
+ * acc: [2][FSRAFT_BN_PARTIAL_ROWS][C] partial rows, ZERO on entry.  res / out / dres / s2d_w as for the entries above.
+ * FSRAFT_ERR_ARG, nothing written: n < 2, C outside 4..256 or no multiple of 4, s2d_w odd or HW / s2d_w odd, out without dres. */
+#define FSRAFT_BN_PARTIAL_ROWS 64
+int fsraft_bnorm_cl_fwd(const float* x, const float* res, const float* weight, const float* bias, const float* cbias,
+                        float* running_mean, float* running_var, float momentum, float eps, float* acc, float* y, float* stats,
+                        int B, int HW, int C, int relu, int s2d_w, hipStream_t stream);
+int fsraft_bnorm_cl_bwd(const float* g, const float* x, const float* stats, const float* out, float* acc, float* dx, float* dres,
+                        float* dweight, float* dbias, int B, int HW, int C, int relu, int s2d_w, hipStream_t stream);
+
+/* ---- the encoders' stem (next-row f3)---------------------------------------------------
  * Replaces `self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3)` and its backward-weights
  * (pytorch/core/extractor.py:135 BasicEncoder, :212 SmallEncoder with 32 outputs).  x [B][3][H][W] planar fp32, w [N][3][7][7],
  * N = 32 or 64; out / dy channels-last [B][Ho][Wo][N] with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1.  The image needs no

@@ -133,6 +133,10 @@ SIGNATURES = {
     "fsraft_affine_relu_fwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, _S],
     "fsraft_affine_relu_bwd": [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, _S],
     "fsraft_sequence_loss": [_PP, _PP, POINTER(c_float), c_int, c_int, c_void_p, c_void_p, c_float, c_float, c_int, c_int, c_int, c_void_p, _S],
+    "fsraft_flow_loss_workspace_bytes": [c_int, c_int, c_int],
+    "fsraft_flow_loss": [_PP, _PP, POINTER(c_float), c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
+                         c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int, c_int, c_int,
+                         c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, _S],
     "fsraft_corr_pool_pyramid": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_pool_pyramid_same": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_lookup_fwd_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],

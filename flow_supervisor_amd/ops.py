@@ -1974,3 +1974,86 @@ def augment_sup(image1, image2, flow, valid, params, crop_hw, flow_mode):
                                       AUG_FLOW_MODES[flow_mode], B, Hs, Ws, params, h, w, *[L.ptr(t) for t in outs], L.ptr(scratch), n,
                                       L.stream()), "augment_sup")
     return outs
+
+
+# ------------------------------------------------------------------ flow losses of the TF tree
+FLOW_PENALTIES = {"l1": 0, "l2": 1, "robust": 2}     # FSRAFT_FLOW_* of include/fsraft.h
+FLOW_LAYOUTS = {"nhwc": (1, 2, 3), "nchw": (2, 3, 1)}   # the dims of H, W and the channels
+
+
+def flow_strides(t, layout):
+    """(bs, cs, ps) in elements of a flow [B,H,W,2] ('nhwc') or [B,2,H,W] ('nchw') whose H and W dims share one pixel stride --
+    contiguous tensors of either shape, the permuted view of the other, the [..., 0:2] slice of a [B,H,W,3] ground truth -- or
+    None where they do not (a crop along W)."""
+    h, w, c = FLOW_LAYOUTS[layout]
+    H, W = t.shape[h], t.shape[w]
+    sh, sw = t.stride(h), t.stride(w)
+    if W > 1 and H > 1 and sh != W * sw:
+        return None
+    return t.stride(0), t.stride(c), (sw if W > 1 else sh if H > 1 else 2)
+
+
+def _mask_strides(m):
+    """(bs, ps) of a [B,H,W] mask, or None."""
+    _, H, W = m.shape
+    sh, sw = m.stride(1), m.stride(2)
+    if W > 1 and H > 1 and sh != W * sw:
+        return None
+    return m.stride(0), (sw if W > 1 else sh if H > 1 else 1)
+
+
+def flow_loss(preds, weights, scale, target=None, mask=None, penalty="l2", layout="nhwc", dpreds=None, metric_idx=None,
+              pixel_out=False, max_flow=400.0, eps=1e-3):
+    """fsraft_flow_loss, one launch: preds n flows of one shape and one set of strides ([B,H,W,2] for layout 'nhwc', [B,2,H,W] for
+    'nchw'); target a flow of that shape with strides of its own, or None (zero flow); mask [B,H,W] or None (ones); dpreds None
+    or a list of tensors with the predictions' strides (entries may be None) that receive scale * weights[i] * m * psi'(d).
+    Returns (out [1] = scale * sum_i weights[i] sum m psi(d), sample_stats [B,2] = (sum mask * epe, sum mask) of prediction
+    metric_idx or None, the [B,H,W] map m * mean_c psi(d) of the single prediction or None).  The outputs and the workspace are
+    one zero-filled allocation."""
+    L.require_cuda_f32(*preds, target, mask, *(dpreds or ()))
+    if penalty not in FLOW_PENALTIES or layout not in FLOW_LAYOUTS:
+        raise RuntimeError(f"flow_loss: penalty {penalty!r}, layout {layout!r}")
+    n = len(preds)
+    h, w, c = FLOW_LAYOUTS[layout]
+    shape = tuple(preds[0].shape)
+    if len(shape) != 4 or shape[c] != 2:
+        raise RuntimeError(f"flow_loss: layout {layout!r} takes two-channel flows, got {shape}")
+    B, H, W = shape[0], shape[h], shape[w]
+    ps = flow_strides(preds[0], layout)
+    if ps is None or any(tuple(p.shape) != shape or p.stride() != preds[0].stride() for p in preds):
+        raise RuntimeError("flow_loss: the predictions share one shape and one set of strides with a single pixel stride")
+    for d in dpreds or ():
+        if d is not None and (tuple(d.shape) != shape or d.stride() != preds[0].stride()):
+            raise RuntimeError("flow_loss: a gradient has the shape and strides of its prediction")
+    ts = (0, 0, 0)
+    if target is not None:
+        ts = flow_strides(target, layout)
+        if tuple(target.shape) != shape or ts is None:
+            raise RuntimeError(f"flow_loss: target {tuple(target.shape)} against predictions {shape}")
+    ms = (0, 0)
+    if mask is not None:
+        ms = _mask_strides(mask) if tuple(mask.shape) == (B, H, W) else None
+        if ms is None:
+            raise RuntimeError(f"flow_loss: mask {tuple(mask.shape)} with strides {mask.stride()} against [{B},{H},{W}]")
+    if pixel_out and n != 1:
+        raise RuntimeError("flow_loss: the per-pixel map is that of a single prediction")
+    nbytes = _lib().fsraft_flow_loss_workspace_bytes(B, H, W)
+    if nbytes == 1:
+        raise RuntimeError(f"libfsraft: flow_loss_workspace_bytes({B}, {H}, {W}) failed with status 1 (bad argument)")
+    nw = nbytes // 4
+    buf = torch.zeros(nw + 2 + 2 * B, device=preds[0].device, dtype=torch.float32)
+    out = buf[nw:nw + 1]
+    stats = buf[nw + 2:].view(B, 2) if metric_idx is not None else None
+    pix = torch.empty(B, H, W, device=preds[0].device, dtype=torch.float32) if pixel_out else None
+    pp, keep_p = L.ptr_array(preds)
+    if dpreds is not None:
+        arr = (ctypes.c_void_p * n)(*[d.data_ptr() if d is not None else None for d in dpreds])
+        dd = ctypes.cast(arr, L._PP)
+    else:
+        dd = None
+    a_w = (ctypes.c_float * n)(*[float(x) for x in weights])
+    L.check(_lib().fsraft_flow_loss(pp, dd, a_w, n, *ps, L.ptr(target), *ts, L.ptr(mask), *ms, FLOW_PENALTIES[penalty], float(max_flow),
+                                    float(eps), float(scale), B, H, W, L.ptr(out), L.ptr(stats),
+                                    -1 if metric_idx is None else int(metric_idx), L.ptr(pix), L.ptr(buf), nbytes, L.stream()),
+            "flow_loss")
+    return out, stats, pix

@@ -6,6 +6,9 @@
     transpose_volume(c_volume)  == tf.transpose(c_volume, [0, 3, 4, 1, 2])                           raft/semi.py:250, 257
     raft.upsample.UpsampleConvexWithMask(scale=8).call([x, mask, ref])                               raft/upsample.py:4-41
     raft.smurf_models.raft_update.BasicUpdateBlock(args, hidden_dim).call([net, inp, corr, flow])    raft_update.py:180-212
+    raft.loss.FlowLossL1 / FlowLossL2 / FlowLossRobust(reduction).__call__(y_true, y_pred)           raft/loss.py:4-93
+    raft.metric.EPE / SparseEPE                                                                      raft/metric.py:3-87
+    flow_sequence_loss, semi_objective: the sums Semisupervised.train_step forms of them             raft/semi.py:373-405, 447-471
 
 TensorFlow is not installed here, so these take and return torch tensors laid out the way the TF code lays
 them out (channels last, coords as [B,H,W,2] with (x, y) in the last dim) and run the same HIP kernels as the
@@ -20,4 +23,6 @@ with it off, the default, such a call that wants a gradient raises.
 """
 from .api import (BasicUpdateBlock, CorrBlock, UpsampleConvexWithMask, build_pyramid, calc_all_field,  # noqa: F401
                   same_grad, transpose_volume)
+from .loss import FlowLossL1, FlowLossL2, FlowLossRobust, flow_sequence_loss, semi_objective  # noqa: F401
+from .metric import EPE, SparseEPE  # noqa: F401
 from .visualize import visualize_flow, visualize_flows  # noqa: F401    util/visualize.py:5-27, 40-42 (HSV flow coding)

@@ -425,6 +425,39 @@ int fsraft_sequence_loss(const float* const* pred, float* const* dpred, const fl
                          const float* gt, const float* valid, float max_flow, float eps, int B, int H, int W, float* out,
                          hipStream_t stream);
 
+/* ---- flow losses of the TensorFlow trainers (raft/loss.py FlowLossL1 / FlowLossL2 / FlowLossRobust over a sequence of
+ * predictions, raft/semi.py:373-405, 447-471; raft/metric.py EPE; csrc/flow_loss.hip) -----------------------------------
+ * One launch for n (1..32) predictions against one target.  Per pixel and channel, d = pred_i - target:
+ *   m = mask * (sqrt(t0^2 + t1^2) < max_flow)   (the mask is a factor, not thresholded; the comparison is strict)
+ *   psi(d) = |d| (L1), d^2 (L2), sqrt(d^2 + eps^2) (ROBUST)
+ *   out[0] = scale * sum_i weights[i] * sum m * psi(d)                                   (written, not added to)
+ *   dpred[i] = scale * weights[i] * m * psi'(d), every element written (+0 where m == 0); dpred or dpred[i] may be NULL
+ *   sample_stats[b] = (sum mask * |pred[metric_idx] - target|_2, sum mask) of sample b (NULL: none; the cut does not enter)
+ *   pixel_out[b][y][x] = m * (psi(d_0) + psi(d_1)) / 2, contiguous [B][H][W], only with n == 1 (NULL: none)
+ * scale = 1 / (2 B H W): Keras' mean over the channel axis and SUM_OVER_BATCH_SIZE; scale = 1 / 2: the gradient of the SUM of a
+ * Reduction.NONE loss.  Strides are in elements: (batch, channel, pixel) shared by all predictions and their gradients, a triple
+ * of its own for the target, (batch, pixel) for the mask; pixel y * W + x of sample b, channel c is at b * bs + (y * W + x) * ps
+ * + c * cs.  [B,H,W,2]: (2HW, 1, 2); [B,2,H,W]: (2HW, HW, 1); a [B,H,W,3] ground truth in place: target (3HW, 1, 3), mask =
+ * base + 2 with (3HW, 3).  target NULL: zero flow, no cut; mask NULL: ones.  Both floats of a pixel are one 8-byte access when
+ * cs == 1, bs and ps are even and every base is 8-byte aligned, two 4-byte accesses otherwise.
+ * workspace: fsraft_flow_loss_workspace_bytes(B, H, W) bytes (>= 64; 1 = bad sizes), 8-byte aligned, whose first 4 bytes are
+ * zero before the first launch that uses it; every launch leaves them zero, so a workspace is reusable by launches that do not
+ * overlap.  Overlapping launches (two streams) take two workspaces; no other state is shared.  The sums are the float64 total,
+ * in workgroup order, of per-workgroup fp32 partial sums: the same bits for the same inputs.
+ * FSRAFT_ERR_ARG before any HIP call for: n outside 1..32, an unknown penalty, NULL pred / pred[i] / weights / out / workspace,
+ * a workspace too small or misaligned, pixel_out with n != 1, sample_stats with metric_idx outside [0, n), B > 65535. */
+#define FSRAFT_FLOW_L1 0
+#define FSRAFT_FLOW_L2 1
+#define FSRAFT_FLOW_ROBUST 2
+int fsraft_flow_loss_workspace_bytes(int B, int H, int W);
+int fsraft_flow_loss(const float* const* pred, float* const* dpred, const float* weights, int n,
+                     int64_t pred_bs, int64_t pred_cs, int64_t pred_ps,
+                     const float* target, int64_t target_bs, int64_t target_cs, int64_t target_ps,
+                     const float* mask, int64_t mask_bs, int64_t mask_ps,
+                     int penalty, float max_flow, float eps, float scale, int B, int H, int W,
+                     float* out, float* sample_stats, int metric_idx, float* pixel_out,
+                     void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- warm start (a step next to the path: pytorch/core/utils/utils.py:26-54 forward_interpolate, called between the
  * frames of a sequence at pytorch/evaluate.py:43) -------------------------------------------------------------------
  * flow [2][H][W] (dx plane, dy plane) at the resolution the flow lives on: every vector is carried to (x + dx, y + dy),

@@ -137,6 +137,10 @@ SIGNATURES = {
     "fsraft_flow_loss": [_PP, _PP, POINTER(c_float), c_int, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64,
                          c_void_p, c_int64, c_int64, c_int, c_float, c_float, c_float, c_int, c_int, c_int,
                          c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, _S],
+    "fsraft_box_copy": [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _IP] + [c_int64] * 8 + [_S],
+    "fsraft_resize_bilinear_fwd": [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_int] + [c_int64] * 8 + [POINTER(c_float), _S],
+    "fsraft_resize_bilinear_bwd": [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_int] + [c_int64] * 8 + [POINTER(c_float), _S],
+    "fsraft_pad_edge": [_PP, _PP, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int] + [c_int64] * 8 + [_S],
     "fsraft_corr_pool_pyramid": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_pool_pyramid_same": [_PP, c_int, c_int64, c_int, c_int, _S],
     "fsraft_corr_lookup_fwd_same": [_PP, c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, _S],

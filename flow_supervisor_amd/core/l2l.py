@@ -14,7 +14,14 @@ from .corr import CorrBlock
 from .gma import mark_records
 from .raft import RAFT, normalise, refine
 from .update import BasicUpdateBlock, to_channels_last
+from .. import image_ops
 from .._lib import on_tensor_device
+
+# The per-sample branches below on csrc/image_ops.hip (fsraft_box_copy): _pad_state is two launches (the hidden state channels
+# last, the flow planar) instead of 2B F.pad and two cat, _crop_back of ALL the supervisor's predictions one list node instead of
+# B strided copies per prediction (and a zero fill + B copies each in backward).  Copies: the same bits either way.  False:
+# the framework composition.  The equal-offset branches (one F.pad, one slice view) do not depend on it.
+BOX_OPS = True
 
 
 def _offsets(v, B):
@@ -38,6 +45,13 @@ def _pad_state(net, flow, ox_l, oy_l, orig, targ):
     if len(set(zip(ox_l, oy_l))) == 1:
         l, r, t, b = pads(ox_l[0], oy_l[0])
         return F.pad(net, (0, 0, l, r, t, b)), F.pad(flow, (l, r, t, b))
+    every = [pads(ox_, oy_) for ox_, oy_ in zip(ox_l, oy_l)]
+    frames = {(t + net.shape[1] + b, l + net.shape[2] + r) for l, r, t, b in every}
+    if BOX_OPS and len(frames) == 1 and min(map(min, every)) >= 0:      # (frames of different sizes: the cat below says so)
+        frame = frames.pop()
+        yx = image_ops.window_offsets([(oy_ // 8, ox_ // 8) for ox_, oy_ in zip(ox_l, oy_l)], net.shape[0], frame, tuple(net.shape[1:3]))
+        return (image_ops.BoxCopyFn.apply(yx, frame, True, "nhwc", net)[0],
+                image_ops.BoxCopyFn.apply(yx, frame, True, "nchw", flow)[0])
     nets, flows = [], []
     for i, (ox_, oy_) in enumerate(zip(ox_l, oy_l)):
         l, r, t, b = pads(ox_, oy_)
@@ -70,10 +84,22 @@ class _CropBackFn(torch.autograd.Function):
 
 
 def _crop_back(flow_up, ox_l, oy_l, orig):
-    """The supervisor's full-frame prediction cut back to the student's window (l2l.py:124-125)."""
+    """The supervisor's full-frame prediction(s) cut back to the student's window (l2l.py:124-125): a tensor, or a list of them
+    (a list comes back as a list; with per-sample offsets and BOX_OPS it is one autograd node per 32 predictions)."""
+    if isinstance(flow_up, (list, tuple)):
+        preds = list(flow_up)
+        if not BOX_OPS or not preds or len(set(zip(ox_l, oy_l))) == 1:
+            return [_crop_back(p, ox_l, oy_l, orig) for p in preds]
+        yx = image_ops.window_offsets(list(zip(oy_l, ox_l)), preds[0].shape[0], tuple(preds[0].shape[-2:]), orig)
+        out = []
+        for i in range(0, len(preds), image_ops.MAX_LIST):
+            out += image_ops.BoxCopyFn.apply(yx, tuple(orig), False, "nchw", *preds[i:i + image_ops.MAX_LIST])
+        return out
     orig_h, orig_w = orig
     if len(set(zip(ox_l, oy_l))) == 1:
         return flow_up[:, :, oy_l[0]: oy_l[0] + orig_h, ox_l[0]: ox_l[0] + orig_w]
+    if BOX_OPS:
+        return _crop_back([flow_up], ox_l, oy_l, orig)[0]
     return _CropBackFn.apply(flow_up, ox_l, oy_l, orig)
 
 
@@ -153,7 +179,7 @@ class _FlowSupervisor:
         # the deferred mask head + upsampler of each phase, after the caller's gradient mode is back (the unlabelled pass of the
         # flow-supervisor step switches it off for the supervisor's half); the student's first.  The supervisor's full-frame
         # predictions are cut back to the student's window here (l2l.py:124-125).
-        return student() + [_crop_back(p, *crop) for p in supervisor()]
+        return student() + _crop_back(supervisor(), *crop)
 
 
 class L2L(_FlowSupervisor, RAFT):

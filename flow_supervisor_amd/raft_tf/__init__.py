@@ -9,6 +9,8 @@
     raft.loss.FlowLossL1 / FlowLossL2 / FlowLossRobust(reduction).__call__(y_true, y_pred)           raft/loss.py:4-93
     raft.metric.EPE / SparseEPE                                                                      raft/metric.py:3-87
     flow_sequence_loss, semi_objective: the sums Semisupervised.train_step forms of them             raft/semi.py:373-405, 447-471
+    crop_bboxes, pad_bboxes (util/image.py:6-49), get_proc_size, resize, resize_flow (raft/__init__.py:199-222),
+    pad_edge, pad_inputs, unpad_inputs (util/pad.py, util/validate.py:301-325): raft_tf/image.py, tensors or lists of them
 
 TensorFlow is not installed here, so these take and return torch tensors laid out the way the TF code lays
 them out (channels last, coords as [B,H,W,2] with (x, y) in the last dim) and run the same HIP kernels as the
@@ -23,6 +25,8 @@ with it off, the default, such a call that wants a gradient raises.
 """
 from .api import (BasicUpdateBlock, CorrBlock, UpsampleConvexWithMask, build_pyramid, calc_all_field,  # noqa: F401
                   same_grad, transpose_volume)
+from .image import (crop_bboxes, get_proc_size, pad_bboxes, pad_edge, pad_inputs, resize, resize_flow,  # noqa: F401
+                    unpad_inputs)
 from .loss import FlowLossL1, FlowLossL2, FlowLossRobust, flow_sequence_loss, semi_objective  # noqa: F401
 from .metric import EPE, SparseEPE  # noqa: F401
 from .visualize import visualize_flow, visualize_flows  # noqa: F401    util/visualize.py:5-27, 40-42 (HSV flow coding)

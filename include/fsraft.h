@@ -814,6 +814,47 @@ int fsraft_axpby(const float* x, float* y, float a, float b, int64_t n, hipStrea
  * split into a per-step context convolution), formed once from the kept per-iteration gradients. */
 int fsraft_sum_n(const float* const* src, int n, float* out, int64_t count, int accumulate, hipStream_t s);
 
+/* ---- image plumbing of the TensorFlow tree (util/image.py:6-49 crop_bboxes / pad_bboxes, raft/__init__.py:199-222 resize /
+ * resize_flow, util/pad.py + util/validate.py:301-325 pad_edge / pad_inputs; csrc/image_ops.hip) ---------------------------
+ * List form: src[i] -> dst[i] for n (1..32) tensors of ONE geometry in one launch.  fp32.  A tensor is [B][H][W][C] read through
+ * four strides in elements (batch, channel, row, x): element (b, c, y, x) is at b * bs + c * cs + y * rs + x * xs.  NHWC is
+ * (HWC, 1, WC, C), planar [B][C][H][W] is (CHW, HW, W, 1); the two sides of a call have strides of their own.  Enqueue only: no
+ * allocation, no synchronisation, no read back.  FSRAFT_ERR_ARG before any HIP call for a NULL table or entry, n outside
+ * 1..32, B, C or a size below 1, C * H * W of either side beyond 2^31 - 1, and what each entry names below.
+ *
+ * fsraft_box_copy: sample b's H x W window sits at (yx[2b], yx[2b+1]) = (y, x) of its Hf x Wf frame; yx is a HOST array of 2 * B
+ * ints, read during the call and passed to the kernel by value (64 samples per launch).  place == 0 (gather): src are frames,
+ * dst windows (crop_bboxes; the backward of pad_bboxes).  place != 0: src are windows, dst frames, every frame element outside
+ * the window written +0.0 by the same launch (pad_bboxes; the backward of crop_bboxes).  Bit-exact.  Where both sides are laid
+ * out alike with unit inner strides (cs == 1 and xs == C, or xs == 1), 16-byte aligned bases, outer strides and row lengths
+ * (W * E, Wf * E floats, E = C or 1) that are multiples of 4, a sample whose row start x * E is one too moves 16-byte units;
+ * every other sample moves 4-byte units.  Also an error: yx NULL, a window outside the frame.
+ *
+ * fsraft_resize_bilinear_fwd: tf.image.resize(method 'bilinear', antialias False) from Hi x Wi to Ho x Wo.  Per axis, in float32
+ * as TensorFlow forms them: scale = (float)n_in / (float)n_out, in = (o + 0.5f) * scale - 0.5f (two roundings), lo =
+ * max(floor(in), 0), hi = min(ceil(in), n_in - 1), lerp = in - floor(in); the value is top + (bottom - top) * lerp_y with top =
+ * tl + (tr - tl) * lerp_x.  factors (a HOST array of C floats, C <= 8, or NULL) multiply channel c behind the interpolation:
+ * (Wo / Wi, Ho / Hi) makes resize_flow one launch.  The s_ strides describe the Hi x Wi side, the d_ strides the Ho x Wo side.
+ * fsraft_resize_bilinear_bwd: its exact transpose.  ddst are the upstream gradients (Ho x Wo, d_ strides), dsrc (Hi x Wi, s_
+ * strides) receive them: every element written, each a sum over the destination pixels whose taps reach it, rows ascending,
+ * columns ascending inside, no atomics: the same bits twice; +0.0 where no tap reaches.  Also an error: B > 65535, factors with
+ * C > 8.
+ *
+ * fsraft_pad_edge: np.pad(x, ((0,0), (top, bottom), (left, right), (0,0)), 'edge'): dst is (H + top + bottom) x (W + left + right).
+ * Bit-exact.  Also an error: a negative pad, B > 65535. */
+int fsraft_box_copy(const float* const* src, float* const* dst, int n, int place, int B, int C, int Hf, int Wf, int H, int W,
+                    const int* yx, int64_t f_bs, int64_t f_cs, int64_t f_rs, int64_t f_xs,
+                    int64_t w_bs, int64_t w_cs, int64_t w_rs, int64_t w_xs, hipStream_t stream);
+int fsraft_resize_bilinear_fwd(const float* const* src, float* const* dst, int n, int B, int C, int Hi, int Wi, int Ho, int Wo,
+                               int64_t s_bs, int64_t s_cs, int64_t s_rs, int64_t s_xs,
+                               int64_t d_bs, int64_t d_cs, int64_t d_rs, int64_t d_xs, const float* factors, hipStream_t stream);
+int fsraft_resize_bilinear_bwd(const float* const* ddst, float* const* dsrc, int n, int B, int C, int Hi, int Wi, int Ho, int Wo,
+                               int64_t s_bs, int64_t s_cs, int64_t s_rs, int64_t s_xs,
+                               int64_t d_bs, int64_t d_cs, int64_t d_rs, int64_t d_xs, const float* factors, hipStream_t stream);
+int fsraft_pad_edge(const float* const* src, float* const* dst, int n, int B, int C, int H, int W,
+                    int top, int bottom, int left, int right, int64_t s_bs, int64_t s_cs, int64_t s_rs, int64_t s_xs,
+                    int64_t d_bs, int64_t d_cs, int64_t d_rs, int64_t d_xs, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,9 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) float lds[Cfg::LDS_FLOATS];
   const int n0 = blockIdx.x * Cfg::BN, m0 = blockIdx.y * Cfg::BM, b = blockIdx.z;
   const float* A = g.A + b * g.sA + (int64_t)m0 * g.lda;
-  RowMajorTileLoader<Cfg::BM, Cfg::BK, Cfg::LDA> la{A, g.lda, g.M - m0, g.K, (g.lda % 4 == 0) && (g.K % 4 == 0)};
+  // the vector loaders need 16-byte addresses: pitch, base and batch stride (the host sends misaligned calls here)
+  const bool a16 = ((uintptr_t)g.A % 16 == 0) && (g.sA % 4 == 0), b16 = ((uintptr_t)g.Bm % 16 == 0) && (g.sB % 4 == 0);
+  RowMajorTileLoader<Cfg::BM, Cfg::BK, Cfg::LDA> la{A, g.lda, g.M - m0, g.K, (g.lda % 4 == 0) && (g.K % 4 == 0) && a16};
   f32x16 acc[Cfg::TM][Cfg::TN];
 #pragma unroll
   for (int i = 0; i < Cfg::TM; ++i)
@@ -36,11 +38,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g) {
   const int KT = (g.K + Cfg::BK - 1) / Cfg::BK;
   if constexpr (BT) {
     RowMajorTileLoader<Cfg::BN, Cfg::BK, Cfg::LDB> lb{g.Bm + b * g.sB + (int64_t)n0 * g.ldb, g.ldb, g.N - n0, g.K,
-                                                      (g.ldb % 4 == 0) && (g.K % 4 == 0)};
+                                                      (g.ldb % 4 == 0) && (g.K % 4 == 0) && b16};
     gemm_mainloop<Cfg>(lds, KT, la, lb, acc);
   } else {
     KMajorTileLoader<Cfg::BN, Cfg::BK, Cfg::LDB> lb{g.Bm + b * g.sB + n0, g.ldb, g.N - n0, g.K,
-                                                    (g.ldb % 4 == 0) && (g.N % 4 == 0)};
+                                                    (g.ldb % 4 == 0) && (g.N % 4 == 0) && b16};
     gemm_mainloop<Cfg>(lds, KT, la, lb, acc);
   }
   float* C = g.C + b * g.sC;

@@ -173,7 +173,9 @@ __global__ __launch_bounds__(256) void nhwc_to_flow_kernel(const float* __restri
   *d = accumulate ? *d + v : v;
 }
 
-// g[m][c] *= (y[m][c] > 0)     (ReLU backward, in place on the incoming gradient)
+// g[m][c] = y[m][c] > 0 ? g[m][c] : 0 for c < C   (ReLU backward, in place on the incoming gradient).  The last chunk of a row
+// with C % 4 != 0 reaches into columns C .. roundup4(C) - 1 (inside the row: ldg, ldy are multiples of 4 and >= C); those lanes
+// are stored back with the bits they were loaded with, whatever y holds there.
 __global__ __launch_bounds__(256) void relu_bwd_kernel(float* __restrict__ g, int ldg, const float* __restrict__ y,
                                                        int ldy, int64_t M, int C) {
   const int c4n = (C + 3) / 4;
@@ -183,7 +185,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(float* __restrict__ g, in
     f32x4 gv = *reinterpret_cast<f32x4*>(g + m * ldg + c);
     const f32x4 yv = *reinterpret_cast<const f32x4*>(y + m * ldy + c);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) gv[i] = yv[i] > 0.f ? gv[i] : 0.f;
+    for (int i = 0; i < 4; ++i) gv[i] = (yv[i] > 0.f || c + i >= C) ? gv[i] : 0.f;
     *reinterpret_cast<f32x4*>(g + m * ldg + c) = gv;
   }
 }
@@ -320,12 +322,15 @@ __global__ __launch_bounds__(256) void sum_n_kernel(SumNArgs a, float* __restric
 }
 
 inline int grid_for(int64_t work) { int64_t g = (work + 255) / 256; return (int)(g < 1 ? 1 : g > 16384 ? 16384 : g); }
+bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }                 // (true for a null pointer: optional operands)
 
 }  // namespace
 
 // src [B][H][W][C] -> dst [B][H/2][W/2][2][2][C] (inverse != 0: the other way; H, W are the full-resolution sizes).
 extern "C" int fsraft_space_to_depth2(const float* src, float* dst, int B, int H, int W, int C, int inverse, hipStream_t s) {
-  if (!src || !dst || src == dst || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 4 || (C & 3)) return FS_ERR_ARG;
+  if (!src || !dst || src == dst || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 4 || (C & 3) || !al16(src) ||
+      !al16(dst))
+    return FS_ERR_ARG;
   int64_t blocks = ((int64_t)B * H * W * (C / 4) + 255) / 256;
   if (blocks > 16384) blocks = 16384;
   if (inverse) hipLaunchKernelGGL((s2d_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, src, dst, B, H, W, C);
@@ -335,19 +340,19 @@ extern "C" int fsraft_space_to_depth2(const float* src, float* dst, int B, int H
 
 extern "C" int fsraft_nchw_to_nhwc(const float* src, float* dst, int B, int C, int HW, int ld, int coff, int accumulate,
                                    hipStream_t s) {
-  if (!src || !dst || B < 1 || C < 1 || HW < 1) return FS_ERR_ARG;
+  if (!src || !dst || B < 1 || B > 65535 || C < 1 || HW < 1 || coff < 0 || coff > ld - C) return FS_ERR_ARG;   // (B: grid.z)
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(ceil_div(HW, 32), ceil_div(C, 32), B), dim3(256), 0, s, src, dst, C, HW, ld, coff, accumulate);
   return fs_launch_status();
 }
 extern "C" int fsraft_nhwc_to_nchw(const float* src, float* dst, int B, int C, int HW, int ld, int coff, int accumulate,
                                    hipStream_t s) {
-  if (!src || !dst || B < 1 || C < 1 || HW < 1) return FS_ERR_ARG;
+  if (!src || !dst || B < 1 || B > 65535 || C < 1 || HW < 1 || coff < 0 || coff > ld - C) return FS_ERR_ARG;
   hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(ceil_div(HW, 32), ceil_div(C, 32), B), dim3(256), 0, s, src, dst, C, HW, ld, coff, accumulate);
   return fs_launch_status();
 }
 extern "C" int fsraft_im2col7(const float* flow, int64_t bs, int64_t cs, int64_t ps, float* cols, int ld, int B, int H,
                               int W, hipStream_t s) {
-  if (!flow || !cols || ld < 100 || ld % 4) return FS_ERR_ARG;
+  if (!flow || !cols || ld < 100 || ld % 4 || B < 1 || H < 1 || W < 1) return FS_ERR_ARG;
   if (((uintptr_t)cols & 15) == 0)
     hipLaunchKernelGGL(im2col7_v4_kernel, dim3(grid_for((int64_t)B * H * W * (ld / 4))), dim3(256), 0, s, flow, bs, cs, ps, cols, ld, B, H, W);
   else
@@ -355,35 +360,33 @@ extern "C" int fsraft_im2col7(const float* flow, int64_t bs, int64_t cs, int64_t
   return fs_launch_status();
 }
 extern "C" int fsraft_col2im7(const float* dcols, int ld, float* dflow, int B, int H, int W, int accumulate, hipStream_t s) {
-  if (!dcols || !dflow) return FS_ERR_ARG;
+  if (!dcols || !dflow || ld < 98 || B < 1 || H < 1 || W < 1) return FS_ERR_ARG;
   const int64_t total = (int64_t)B * 2 * H * W;
   hipLaunchKernelGGL(col2im7_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, dcols, ld, dflow, B, H, W, accumulate);
   return fs_launch_status();
 }
 extern "C" int fsraft_flow_to_nhwc(const float* flow, int64_t bs, int64_t cs, int64_t ps, float* dst, int ld, int coff,
                                    int B, int HW, hipStream_t s) {
-  if (!flow || !dst) return FS_ERR_ARG;
+  if (!flow || !dst || B < 1 || HW < 1 || coff < 0 || coff > ld - 2) return FS_ERR_ARG;
   const int64_t M = (int64_t)B * HW;
   hipLaunchKernelGGL(flow_to_nhwc_kernel, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, s, flow, bs, cs, ps, dst, ld, coff, M, HW);
   return fs_launch_status();
 }
 extern "C" int fsraft_nhwc_to_flow(const float* src, int ld, int coff, float* dflow, int B, int HW, int accumulate, hipStream_t s) {
-  if (!src || !dflow) return FS_ERR_ARG;
+  if (!src || !dflow || B < 1 || HW < 1 || coff < 0 || coff > ld - 2) return FS_ERR_ARG;
   const int64_t M = (int64_t)B * HW;
   hipLaunchKernelGGL(nhwc_to_flow_kernel, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, s, src, ld, coff, dflow, M, HW, accumulate);
   return fs_launch_status();
 }
 extern "C" int fsraft_relu_bwd(float* g, int ldg, const float* y, int ldy, int64_t M, int C, hipStream_t s) {
-  if (!g || !y || ldg % 4 || ldy % 4) return FS_ERR_ARG;
+  // (16-byte chunks of rows of g and y: aligned bases, pitches in whole chunks, and a last chunk that ends inside its row)
+  if (!g || !y || ldg % 4 || ldy % 4 || !al16(g) || !al16(y) || C < 1 || C > ldg || C > ldy) return FS_ERR_ARG;
   hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(M * ((C + 3) / 4))), dim3(256), 0, s, g, ldg, y, ldy, M, C);
   return fs_launch_status();
 }
-namespace {
-bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-}
 extern "C" int fsraft_gru_bwd1(const float* dhn, const float* dhn2, const float* z, const float* q, const float* h, float* dzr, int ldzr,
                                float* dq, float* dh, float* dzr_sum, float* dq_sum, int64_t M, int hid, hipStream_t s) {
-  if (!dhn || !z || !q || !h || !dzr || !dq || !dh) return FS_ERR_ARG;
+  if (!dhn || !z || !q || !h || !dzr || !dq || !dh || hid < 1 || ldzr < 2 * hid) return FS_ERR_ARG;
   const bool v4 = hid % 4 == 0 && ldzr % 4 == 0 && al16(dhn) && al16(dhn2) && al16(z) && al16(q) && al16(h) && al16(dzr) && al16(dq) &&
                   al16(dh) && al16(dzr_sum) && al16(dq_sum);
   if (!v4 && dhn2) return FS_ERR_ARG;            // (the second summand exists for the vectorised kernel only)
@@ -394,14 +397,14 @@ extern "C" int fsraft_gru_bwd1(const float* dhn, const float* dhn2, const float*
 }
 extern "C" int fsraft_gru_bwd2(const float* drh, const float* r, const float* h, float* dzr, int ldzr, float* dh,
                                float* dzr_sum, int64_t M, int hid, hipStream_t s) {
-  if (!drh || !r || !h || !dzr || !dh) return FS_ERR_ARG;
+  if (!drh || !r || !h || !dzr || !dh || hid < 1 || ldzr < 2 * hid) return FS_ERR_ARG;
   if (hid % 4 == 0 && ldzr % 4 == 0 && al16(drh) && al16(r) && al16(h) && al16(dzr) && al16(dh) && al16(dzr_sum))
     hipLaunchKernelGGL(gru_bwd2_v4_kernel, dim3(grid_for(M * (hid / 4))), dim3(256), 0, s, drh, r, h, dzr, ldzr, dh, dzr_sum, M, hid);
   else hipLaunchKernelGGL(gru_bwd2_kernel, dim3(grid_for(M * hid)), dim3(256), 0, s, drh, r, h, dzr, ldzr, dh, dzr_sum, M, hid);
   return fs_launch_status();
 }
 extern "C" int fsraft_col_sum(const float* x, int ld, int64_t M, int C, float* out, float scale, hipStream_t s) {
-  if (!x || !out) return FS_ERR_ARG;
+  if (!x || !out || C < 1 || C > ld) return FS_ERR_ARG;
   int ysplit = (int)(M / 128); if (ysplit < 1) ysplit = 1; if (ysplit > 2048) ysplit = 2048;
   hipLaunchKernelGGL(col_sum_kernel, dim3(ceil_div(C, 64), ysplit), dim3(256), 0, s, x, ld, M, C, out, scale);
   return fs_launch_status();

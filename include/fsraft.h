@@ -791,7 +791,12 @@ int fsraft_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, float* 
  * binding keys per-capture scratch (zero-filled accumulation targets) on it. */
 int fsraft_stream_capture_id(hipStream_t stream, unsigned long long* id);
 
-/* ---- layout / elementwise helpers around the GEMMs ----------------------------------- */
+/* ---- layout / elementwise helpers around the GEMMs -----------------------------------
+ * FSRAFT_ERR_ARG before any launch for a NULL required pointer and for what a kernel makes no provision for: a channel window
+ * outside its row (coff < 0, coff + C > ld; C > ld for relu_bwd and col_sum; ldzr < 2 hid), sizes below 1 where the grid is formed
+ * from them, pitches that are no multiple of 4 floats and bases off 16 bytes where 16-byte chunks are moved (relu_bwd: g, y, ldg,
+ * ldy; space_to_depth2: src, dst, C; im2col7: ld; sum_n: everything), col2im7's ld < 98.  relu_bwd: g[m][c] = y[m][c] > 0 ?
+ * g[m][c] : 0 for c < C and nothing else -- columns C .. ld - 1 of g keep their bits. */
 int fsraft_nchw_to_nhwc(const float* src, float* dst, int B, int C, int HW, int ld, int coff, int accumulate, hipStream_t s);
 /* Space-to-depth by 2 of a channels-last tensor: dst[b][y/2][x/2][(y%2)*2 + x%2][c] = src[b][y][x][c] (inverse != 0: back).
  * A stride-2 3x3 / 1x1 convolution over src (pytorch/core/extractor.py:13, 39: the first convolution and the shortcut of a
